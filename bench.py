@@ -11,6 +11,15 @@ solve + back-substitution + trial evaluation, rejected trial steps counted insid
 continues until exactly K iterations were timed.  Inputs are resident in HBM before timing.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config config3] [--form pair|dedup]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K iterations and prints the result line (metric, value, unit, ms_per_step,
+...).  `--dump-outputs DIR` writes what the timed path returned in its last step -- the device state a caller reads
+back with get_state (DIR/ptz.npy, DIR/rays.npy) and the last solve's [cost, initial_cost] (DIR/cost.npy), float64 --
+right after the timed region; the inputs are the seed-0 synthetic problem, identical from run to run.  `--full` adds
+every secondary leg after the timed region (dedicated and cold-cache K1 passes, the kernel breakdown, the roofline, the
+accuracy gates, the fp64 / linear-loss leg, the drop-in call, config 4, the CPU baseline, the config-5 stream); the
+`--no-*`, `--config4-steps` and `--stream-frames` options thin a `--full` run.
 
 N > 1 (one process per GPU): `--gpus N` without a torch.distributed environment re-launches this script
 under `python -m torch.distributed.run --nproc-per-node N` (a child process, started before anything
@@ -67,7 +76,17 @@ def parse():
     ap.add_argument("--stream-frames", type=int, default=300,
                     help="config-5 leg: frames of demo_stream.py after the headline (0: skip); 300 = 60 keyframes, so the "
                          "30-keyframe sliding window is full for the second half (100 frames never fill it)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every secondary leg (K1 passes, kernel breakdown, roofline, "
+                         "accuracy, fp64 leg, drop-in call, config 4, CPU baseline, stream); a plain run times the "
+                         "headline only")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_accuracy = a.no_secondary = a.no_cold = True
+        a.config4_steps = a.stream_frames = 0
+    return a
 
 
 def _free_port():
@@ -204,6 +223,18 @@ def stream_leg(frames):
     return {k: d[k] for k in keep if k in d}
 
 
+def dump_outputs(out_dir, h, res):
+    """--dump-outputs: the timed path's last step as a caller receives it -- the state read back from the device
+    (get_state: poses [n_pose, 3] = pan, tilt, f; rays [n_landmark, 2]) and the last solve's [cost, initial_cost] -- as
+    float64 .npy files (config 3: 0.3 MB in all).  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    ptz, rays = h.get_state()
+    arrays = {"ptz": ptz, "rays": rays, "cost": np.array([res.cost, res.initial_cost])}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
 def _git_blob(path):
     """Provenance of a committed measurement file: its git blob id (None outside a checkout)."""
     try:
@@ -302,9 +333,10 @@ def setup_leg(cx, cfg):
                 generate_s=t_gen, set_problem_s=t_setup)
 
 
-def run_iters(hh, k, ar=None):
+def run_iters(hh, k, ar=None, last=None):
     """k LM iterations (scipy njev) of restarted ftol=1e-4 solves from the device-resident x0 (ptzba_solve_resident: the
-    restart is enqueued by C the moment the final decision is on the host; PTZBA_BENCH_PYLOOP=1: the Python loop)."""
+    restart is enqueued by C the moment the final decision is on the host; PTZBA_BENCH_PYLOOP=1: the Python loop).
+    `last`: a list that receives the last solve's LMResult."""
     import ptzba
     pyloop = os.environ.get("PTZBA_BENCH_PYLOOP") == "1"
     done = 0
@@ -315,6 +347,8 @@ def run_iters(hh, k, ar=None):
             res = ptzba.LMSolver(hh, ftol=1e-4, xtol=1e-8, max_iter=k - done, allreduce=ar).run()
         else:
             res = hh.solve_resident(restore=True, ftol=1e-4, xtol=1e-8, max_iter=k - done)
+        if last is not None:
+            last[:] = [res]
         done += max(res.njev, 1)
         solves += 1
         if res.njev == 0:
@@ -322,14 +356,14 @@ def run_iters(hh, k, ar=None):
     return done, solves
 
 
-def timed(cx, hh, steps):
+def timed(cx, hh, steps, last=None):
     """Exactly `steps` iterations between a barrier + device synchronisation on both sides; the max over ranks."""
     import torch
     if cx.dist:
         cx.dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    its, nsolve = run_iters(hh, steps)
+    its, nsolve = run_iters(hh, steps, last=last)
     torch.cuda.synchronize()
     if cx.dist:
         cx.dist.barrier()
@@ -485,14 +519,22 @@ def main():
     # record adds a gap to the stream; the launches are identical work); the other groups' events are
     # timed in a separate pass afterwards
     h.reset_kernel_times(True, groups=1, stride=4)
-    iters, solves, elapsed = timed(cx, h, a.steps)
+    last = []
+    iters, solves, elapsed = timed(cx, h, a.steps, last=last)
     k1_ms_region, k1_n_region = h.kernel_times()["linearize"]
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the device state and the last solve's cost
+        dumped = dump_outputs(a.dump_outputs, h, last[0])
     # the roofline's K1 figure: a dedicated pass after the timed region, EVERY K1 launch of K1_PASS_ITERS LM iterations
     # event-bracketed (stride 1), so the figure does not depend on --steps (the in-region sample is kept beside it)
-    h.reset_kernel_times(True, groups=1, stride=1)
-    run_iters(h, K1_PASS_ITERS)
-    k1_ms, k1_n = h.kernel_times()["linearize"]
-    kt, per_rank = breakdown(cx, h, min(5, a.steps))
+    k1_ms = k1_n = 0
+    kt = per_rank = None
+    if a.full:
+        h.reset_kernel_times(True, groups=1, stride=1)
+        run_iters(h, K1_PASS_ITERS)
+        k1_ms, k1_n = h.kernel_times()["linearize"]
+        kt, per_rank = breakdown(cx, h, min(5, a.steps))
     # cold-cache K1: a 1 GiB scratch buffer streamed through the caches before each timed K1 launch (outside its events)
     # evicts L2 and the 256 MB Infinity Cache, so the launch streams its records from HBM (SURVEY §8d caveat): written
     # (rounds 2-4's `cold_cache`: dirty caches whose write-backs run during the launch) and read (round 5 on:
@@ -515,7 +557,7 @@ def main():
     secondary = None
     opt = None
     opt_path = os.path.join(ROOT, "tests", "golden", f"{a.config}_optimum.npz")
-    if os.path.exists(opt_path):
+    if a.full and os.path.exists(opt_path):
         z = np.load(opt_path)
         if int(z["n_records"]) == len(prob.frame) and int(z["frame_sum"]) == int(prob.frame.astype(np.int64).sum()):
             opt = {k: z[k] for k in ("ptz_tight", "rays_tight", "tight_cost", "ptz_tight_huber", "rays_tight_huber",
@@ -612,7 +654,7 @@ def main():
                           "get_state, one cold call (new handle)"}
 
     traffic = traffic_src = None  # PMC passes are taken on the whole problem (N = 1); a shard's launch moves less
-    if world == 1 and os.path.exists(a.traffic_json):
+    if a.full and world == 1 and os.path.exists(a.traffic_json):
         try:
             tj = json.load(open(a.traffic_json))
             key = f"{a.config}/{a.form}/{a.precision}/{a.loss}"
@@ -697,7 +739,15 @@ def main():
                          "frac_layout_bytes": achieved_layout / HBM_PEAK_GBS},
             "kernel_ms": kt,
         }
-        if world > 1:
+        if not a.full:
+            # a plain run has no dedicated K1 pass and no breakdown: only the in-region K1 sample rides along
+            del out["roofline"], out["kernel_ms"]
+            out["k1_avg_ms_timed_region"] = k1_ms_region
+            out["k1_launches_timed_region"] = k1_n_region
+        out["full"] = bool(a.full)
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        if world > 1 and a.full:
             out["per_rank"] = per_rank
             out["collective_fit"] = collective_fit(per_rank)
         if k1_cold_ms:

@@ -14,7 +14,10 @@ TAG=${TAG:-r06}
 CFG=${CFG:-config3}
 mkdir -p gpurun_out
 P=$PWD/pan-tilt-zoom-slam_amd
-BARGS="--steps ${BSTEPS:-100} --warmup 5 --no-cpu-baseline --no-accuracy --stream-frames 0 --no-cold"
+# --full: the summaries below read kernel_ms / per_rank / collective_fit, which a plain bench.py run does not measure
+BARGS="--full --steps ${BSTEPS:-100} --warmup 5 --no-cpu-baseline --no-accuracy --stream-frames 0 --no-cold"
+DIST_ARGS="--full ${DIST_ARGS}"
+FULL_ARGS="--full ${FULL_ARGS}"
 summ() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], 'it/s', round(d['value'],1), 'ms/it', round(d['ms_per_step'],4), {k: round(v,4) for k,v in d['kernel_ms'].items()})" "$1" "$2"; }
 for st in $STEPS; do
   case $st in
