@@ -131,7 +131,7 @@ PTZBA_EXPORT int ptzba_dist_form_estimate(int32_t n_pose, int32_t n_fixed, const
 /* per-iteration scalars read back after ptzba_step (all fp64):
  * [0] cost at the current state, [1] cost at the trial state, [2] predicted reduction,
  * [3] |delta|^2, [4] |x|^2, [5] factorisation status (0 ok, >0 not positive definite),
- * [6] max |gradient| (unscaled), [7] reserved */
+ * [6] max |gradient| (unscaled; over the free poses and the rays), [7] reserved */
 #define PTZBA_NSCALARS 8
 
 /* ---------------- lifecycle ---------------- */
@@ -159,6 +159,10 @@ PTZBA_EXPORT int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_lan
  * [4] reduced-system size [5] landmarks with observations [6] max segments per landmark
  * [7] bytes of device memory held */
 PTZBA_EXPORT int ptzba_problem_info(ptzba_handle h, int64_t* info8);
+/* the linearisation kernel's work split: [0] work items (landmarks with observations, one wave each), [1] workgroups,
+ * [2] workgroups whose landmarks' frame range exceeds the LDS frame table, so they read the tables from global memory,
+ * [3] the largest number of segment windows one landmark is walked in */
+PTZBA_EXPORT int ptzba_k1_info(ptzba_handle h, int64_t* info4);
 /* host phase times of the last ptzba_set_problem (sort, segments, K2 structure, plan, uploads ...): names[k] (static
  * strings) and ms[k] for k < min(cap, *n_out); *n_out = the number of phases recorded */
 PTZBA_EXPORT int ptzba_setup_timing(ptzba_handle h, int32_t cap, const char** names, double* ms, int32_t* n_out);

@@ -51,6 +51,7 @@ struct ptzba_ctx {
   DBuf curv_pred;                // [8] the curvature-mode reduction's output (the trial's landmark-part prediction)
   int64_t n_rec = 0, n_seg = 0;
   int n_work = 0, max_seg_per_lm = 0;
+  int k1_groups = 0, k1_groups_global = 0;  // K1 workgroups; those that read the frame tables from global memory
   int n_sys = 0;
   int64_t ld = 0;
   double u = 0, v = 0;
@@ -1781,6 +1782,18 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
     for (int q = 0; q < 3; ++q) lm_work[8 * k + 4 + q] = lm_meta[4 * l + q];
     lm_work[8 * k + 7] = (int32_t)seg_rec_begin[std::min(lm_seg_begin[l + 1], lm_seg_begin[l] + K1_SEGW)];
   }
+  // which table path each K1 workgroup takes (ptzba_k1_info): the kernel's own frame range and predicate
+  h->k1_groups = (h->n_work + K1_WPB - 1) / K1_WPB;
+  h->k1_groups_global = 0;
+  for (int g = 0; g < h->k1_groups; ++g) {
+    int fmin = n_pose, fmax = -1;
+    for (int q = 0; q < K1_WPB; ++q) {
+      const int k = std::min(g * K1_WPB + q, h->n_work - 1);
+      fmin = std::min(fmin, lm_work[8 * k + 4]);
+      fmax = std::max(fmax, lm_work[8 * k + 5]);
+    }
+    if (!k1_ftl_fits(fmin, fmax)) ++h->k1_groups_global;
+  }
   h->n_sys = 3 * (n_pose - o.n_fixed);
   // system order and factorisation plan (from the coupling window; a sharded problem passes the global one)
   std::vector<int32_t> win(frame_win_hi);
@@ -2036,6 +2049,15 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
   return 0;
 }
 
+int ptzba_k1_info(ptzba_handle h, int64_t* info) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  info[0] = h->n_work;
+  info[1] = h->k1_groups;
+  info[2] = h->k1_groups_global;
+  info[3] = (h->max_seg_per_lm + K1_SEGW - 1) / K1_SEGW;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 static void* ft_real(ptzba_ctx* h) { return h->precision == PTZBA_FP32 ? h->ft.p : h->ft64.p; }
 static void* rt_real(ptzba_ctx* h) { return h->precision == PTZBA_FP32 ? h->rt.p : h->rt64.p; }
@@ -2252,6 +2274,9 @@ static int exchange_run(ptzba_ctx* h, int kind, double* buf, int64_t n) {
   }
   return 0;
 }
+// the trial's reduction (k_reduce_cols): column 0 the trial cost, columns 1-4 lm_red's pred, |d|^2, |x|^2 (sums) and the
+// rays' max |gradient| (a maximum: bit 4) -> scal[1..5]
+constexpr int LM_RED_MAXMASK = 1 << 4;
 static int64_t scal_count(const ptzba_ctx* h) { return h->dist_mode ? 2 * PTZBA_NSCALARS : PTZBA_NSCALARS; }
 
 // the rank tree's group communicators, one split per tree depth 1..depth (collective over ALL ranks of comm, in the
@@ -2451,14 +2476,14 @@ static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* se
     }
   }
   linearize_into(h, nx, sel, 1, nullptr, hc_dev);
-  // scal[1] (trial cost) and scal[2..4] are overwritten below, loc[0..3] by the trial kernel: no memsets
+  // scal[1] (trial cost) and scal[2..5] are overwritten below, loc[0..3] by the trial kernel: no memsets
   if (sel && !h->has_exchange() && !h->ext_exchange && !h->scal_exported && !h->dist_mode) {
     // launched by ptzba_lm_decide with the decision fused into it (nothing runs between the two calls)
     h->scal_deferred = true;
     return 0;
   }
-  launch_reduce_cols(h->lm_out[sel ? 0 : nx].as<double>() + 5, h->n_lm, 8, 1, 0, h->scal.as<double>() + 1,
-                     h->red_scratch.as<double>(), h->st, h->lm_red.as<double>(), 4, 3, h->scal.as<double>() + 2,
+  launch_reduce_cols(h->lm_out[sel ? 0 : nx].as<double>() + 5, h->n_lm, 8, 1, LM_RED_MAXMASK, h->scal.as<double>() + 1,
+                     h->red_scratch.as<double>(), h->st, h->lm_red.as<double>(), 4, 4, h->scal.as<double>() + 2,
                      h->lm_out[1].as<double>() + 5, sel, 1);
   HIPCHK(hipGetLastError());
   // partial scalars (replicated: the landmark sums; part-owned: also the pose partials, each frame counted
@@ -2558,8 +2583,8 @@ int ptzba_lm_decide(ptzba_handle h, int trial) {
     h->scal_deferred = false;
     const int* sel = &h->lmdev.as<LMDev>()->cur;
     const DecideArgs dec{st, h->locp(), h->info.as<int>(), h->lm_host + k, trial + 1};
-    launch_reduce_cols(h->lm_out[0].as<double>() + 5, h->n_lm, 8, 1, 0, h->scal.as<double>() + 1,
-                       h->red_scratch.as<double>(), h->st, h->lm_red.as<double>(), 4, 3, h->scal.as<double>() + 2,
+    launch_reduce_cols(h->lm_out[0].as<double>() + 5, h->n_lm, 8, 1, LM_RED_MAXMASK, h->scal.as<double>() + 1,
+                       h->red_scratch.as<double>(), h->st, h->lm_red.as<double>(), 4, 4, h->scal.as<double>() + 2,
                        h->lm_out[1].as<double>() + 5, sel, 1, &dec);
   } else {
     launch_lm_decide(st, h->scal.as<double>(), h->locp(), h->info.as<int>(), h->lm_host + k, trial + 1,
@@ -2712,7 +2737,7 @@ int ptzba_read_scalars(ptzba_handle h, double* out) {
   out[3] = s[3] + l[1];
   out[4] = s[4] + l[2];
   out[5] = h->dist_mode ? l[4] : h->scal_host[16];  // part-owned: the status summed over ranks
-  out[6] = l[3];
+  out[6] = std::max(l[3], s[5]);  // the gradient's largest entry over the free poses (loc) and the rays (scal)
   out[7] = 0;
   return 0;
 }

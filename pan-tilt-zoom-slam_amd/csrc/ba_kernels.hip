@@ -84,9 +84,7 @@ constexpr int SEGW = K1_SEGW;  // segments per LDS window per wave
 #endif
 // (Round 5 removed the measured-slower build variants: one record per lane (K1_COARSE 0), three record groups in
 // flight (K1_DEPTH 3), LDS-atomic tail runs, issue-order tails and phase C's own table loads (K1_FTV_LATE))
-#ifndef K1_WPB
-#define K1_WPB 4  // waves (landmarks) per workgroup: the frame tables are staged once per workgroup
-#endif
+// (K1_WPB, waves per workgroup: ptzba_kernels.h -- the host counts the workgroups' table paths with it)
 #ifndef K1_MIN_WAVES
 #define K1_MIN_WAVES 4  // waves per SIMD the register budget must allow (occupancy)
 #endif
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
       fbase = min(fbase, m.x);
       fmax = max(fmax, m.y);
     }
-    ftl_ok = fmax - fbase < K1_FT_LDS;  // (else this workgroup reads the tables from global memory)
+    ftl_ok = k1_ftl_fits(fbase, fmax);  // (else this workgroup reads the tables from global memory)
     const double4* src = reinterpret_cast<const double4*>(a.ft64);
     if (ftl_ok)
     for (int e = fbase + (int)threadIdx.x; e <= fmax; e += blockDim.x) {
@@ -863,12 +861,12 @@ __global__ __launch_bounds__(256) void k_reduce_cols(const double* __restrict__ 
     }
   } else if (dec.st) {
     // fused decision (trial-cost reduction of a single-GPU device-driven LM): out = scal + 1 (trial cost), out2 =
-    // scal + 2 (pred, |dx|^2, |x|^2 landmark partials); the sums come from LDS, not from the stores above
+    // scal + 2 (pred, |dx|^2, |x|^2 landmark partials, the rays' max |g|); the sums come from LDS, not from the stores above
     __syncthreads();
     if (threadIdx.x == 0) {
-      double sc[5];
+      double sc[6];
       sc[0] = 0.0;  // (the current cost lives in LMDev)
-      sc[1] = tot[0]; sc[2] = tot[1]; sc[3] = tot[2]; sc[4] = tot[3];
+      sc[1] = tot[0]; sc[2] = tot[1]; sc[3] = tot[2]; sc[4] = tot[3]; sc[5] = tot[4];
       lm_decide_body(dec.st, sc, dec.loc, dec.info, dec.rec, dec.seq, 0);
     }
   }
@@ -950,7 +948,7 @@ __global__ void k_lm_init(LMDev* st, const double* __restrict__ scal, LMParams p
   st->relin = 0;
 }
 
-// scipy trf decision rules (one thread): scal = {cost, trial cost, pred, |dx|^2, |x|^2} partial sums
+// scipy trf decision rules (one thread): scal = {cost, trial cost, pred, |dx|^2, |x|^2} partial sums, rays' max |g|
 __device__ void lm_decide_body(LMDev* st, const double* scal, const double* __restrict__ loc,
                                const int* __restrict__ info, LMDev* __restrict__ rec, int seq, int info_in_loc) {
   LMDev s = *st;
@@ -959,7 +957,7 @@ __device__ void lm_decide_body(LMDev* st, const double* scal, const double* __re
   if (!s.done) {
     const LMParams& p = s.p;
     const double new_cost = scal[1], pred = scal[2] + loc[0], dx2 = scal[3] + loc[1], x2 = scal[4] + loc[2];
-    const double gmax = loc[3];
+    const double gmax = fmax(loc[3], scal[5]);  // free poses (k_trial's pose block) | rays (lm_red column 3)
     s.nfev += 1;
     s.trials += 1;
     // part-owned solve: the factorisation status summed over ranks (loc[4]), so every rank decides alike

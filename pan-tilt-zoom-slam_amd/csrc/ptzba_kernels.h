@@ -13,6 +13,12 @@ constexpr int K1_SEGW = 128;  // K1 segments per LDS window per wave
 // many frames, else the workgroup reads them from global memory.  Round 6: 640 -> 384 frames (15 KB instead of 25 KB),
 // so five workgroups of four waves fit a CU's LDS (38 -> 27 KB per workgroup): 5 waves / SIMD instead of 4
 constexpr int K1_FT_LDS = K1_FT_LDS_N;
+#ifndef K1_WPB
+#define K1_WPB 4  // waves (landmarks) per workgroup: the frame tables are staged once per workgroup
+#endif
+// whether a K1 workgroup whose K1_WPB landmarks see the frames [fmin, fmax] stages the tables in LDS: the one predicate
+// of the kernel (k_linearize) and of the host's count of the workgroups on either path (ptzba_k1_info)
+__host__ __device__ inline bool k1_ftl_fits(int fmin, int fmax) { return fmax - fmin < K1_FT_LDS; }
 // dense landmark x frame slot rows, packed (no padding: K1 writes and K2 reads 60 B per fp32 slot, not 80):
 // W (3x2) in W_STRIDE reals, U (3x3 sym, 6) | g_pose (3) in UG_STRIDE reals; rows are only 4-B (fp32) / 8-B (fp64)
 // aligned, so the vector accesses go through the element-aligned vector types below (dwordx4 / x2 on gfx950)

@@ -335,6 +335,12 @@ __global__ __launch_bounds__(512) void k_schur(SchurArgs a) {
 // and stored as the fp32 split partial (the reduce sums the splits in fp64).  Range: W (~1e4 px^2) and Y = -W V~^-1 (~1) would not both fit fp16, so row
 // k = (landmark, d) of W is scaled by g_l = 2^round(log2 sqrt(tr V~_l^-1)) and the same row of Y by
 // 1 / g_l: the product Y^T W is unchanged (powers of two: exact), both factors ~ sqrt(|W| |Y|).
+// The focal-length rows of both operands are ~2^8 below the pan / tilt rows (d x / d f = (x - u) / f ~ 0.1 against
+// d x / d pan ~ f pi / 180 ~ 50 px / deg), so their lo halves fell below fp16's normal range (6e-5) and kept only a few
+// bits -- at lambda = 0 the undamped step of tests/test_gpu_k1_paths.py was off by up to 8.6e-3 of its largest entry,
+// reproduced to three digits by a CPU emulation of this split.  Those rows are staged times MF_FROW = 2^7 (still below
+// the pan / tilt rows: no new overflow) and the accumulators of the f rows / columns scaled back: exact.
+constexpr float MF_FROW = 128.f;
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef float f4v __attribute__((ext_vector_type(4)));
 constexpr int MKP = 40;
@@ -435,7 +441,8 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
         hp2v h, l;
-        split_pk(P.rw[q][2 * r] * gq, P.rw[q][2 * r + 1] * gq, h, l);
+        const float gr = r == 2 ? gq * MF_FROW : gq;
+        split_pk(P.rw[q][2 * r] * gr, P.rw[q][2 * r + 1] * gr, h, l);
         *reinterpret_cast<hp2v*>(&sWt[buf][0][r * WAVE + ln][2 * j]) = h;
         *reinterpret_cast<hp2v*>(&sWt[buf][1][r * WAVE + ln][2 * j]) = l;
       }
@@ -448,7 +455,8 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
     for (int q = 0; q < 3; ++q) {
       const float W0 = P.ryw[2 * q], W1 = P.ryw[2 * q + 1];
       hp2v h, l;
-      split_pk(-fmaf(W0, v0, W1 * v1), -fmaf(W0, v1, W1 * v2), h, l);
+      const float sq = q == 2 ? -MF_FROW : -1.f;
+      split_pk(sq * fmaf(W0, v0, W1 * v1), sq * fmaf(W0, v1, W1 * v2), h, l);
       *reinterpret_cast<hp2v*>(&sY[buf][0][q * SF + yi][2 * yj]) = h;
       *reinterpret_cast<hp2v*>(&sY[buf][1][q * SF + yi][2 * yj]) = l;
     }
@@ -592,7 +600,8 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
       for (int v = 0; v < 4; ++v) {
         const int row = 16 * (3 * rg + x) + (lane >> 4) * 4 + v, col = 16 * (3 * cg + y) + fr;
         const int q = row / SF, i = row % SF, r = col / WAVE, f2 = col % WAVE;
-        out[(i * 9 + 3 * q + r) * WAVE + f2] = c[x][y][v];
+        const float back = (q == 2 ? 1.f / MF_FROW : 1.f) * (r == 2 ? 1.f / MF_FROW : 1.f);  // (exact: powers of two)
+        out[(i * 9 + 3 * q + r) * WAVE + f2] = c[x][y][v] * back;
       }
   SK_T(10);
 #ifdef SK_TIMING

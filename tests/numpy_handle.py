@@ -121,6 +121,7 @@ class NumpyBAHandle:
         self.scal[2] = float(np.sum((-0.5 * np.sum(L['gl'] * dl, 1) + 0.5 * self.lam * np.sum(Dr * dl * dl, 1))[pres]))
         self.scal[3] = float(np.sum((dl * dl)[pres]))
         self.scal[4] = float(np.sum((self.rays * self.rays)[pres]))
+        self.scal[5] = float(np.max(np.abs(L['gl'][pres]))) if pres.any() else 0.0  # rays' max |g| (ranks: summed, an upper bound)
         self.loc[:] = 0
         self.loc[0] = float(-0.5 * gpose @ dp + 0.5 * self.lam * np.sum(self.D_pose[fx3:] * dp * dp))
         self.loc[1] = float(dp @ dp)
@@ -130,7 +131,7 @@ class NumpyBAHandle:
 
     def read_scalars(self):
         s, l = self.scal, self.loc
-        return np.array([s[0], s[1], s[2] + l[0], s[3] + l[1], s[4] + l[2], float(self.info), l[3], 0.0])
+        return np.array([s[0], s[1], s[2] + l[0], s[3] + l[1], s[4] + l[2], float(self.info), max(l[3], s[5]), 0.0])
 
     def accept(self, ok):
         if ok:
@@ -251,6 +252,7 @@ class NumpyPartHandle(NumpyBAHandle):
         self.scal[2] = float(np.sum((-0.5 * np.sum(L['gl'] * dl, 1) + 0.5 * self.lam * np.sum(Dr * dl * dl, 1))[pres]))
         self.scal[3] = float(np.sum((dl * dl)[pres]))
         self.scal[4] = float(np.sum((self.rays * self.rays)[pres]))
+        self.scal[5] = float(np.max(np.abs(L['gl'][pres]))) if pres.any() else 0.0  # rays' max |g| (ranks: summed, an upper bound)
         cr = self.counted[fx:].repeat(3)  # counted free rows
         self.loc[:] = 0
         self.loc[0] = float(np.sum((-0.5 * gpose * dp + 0.5 * self.lam * D * dp * dp)[cr]))
@@ -264,7 +266,7 @@ class NumpyPartHandle(NumpyBAHandle):
 
     def read_scalars(self):
         s, l = self.scal, self.loc
-        return np.array([s[0], s[1], s[2] + l[0], s[3] + l[1], s[4] + l[2], l[4], l[3], 0.0])
+        return np.array([s[0], s[1], s[2] + l[0], s[3] + l[1], s[4] + l[2], l[4], max(l[3], s[5]), 0.0])
 
     def accept(self, ok):
         if ok:
