@@ -387,6 +387,40 @@ PTZBA_EXPORT int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, 
                                   const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
                                   int32_t* status_out);
 
+/* ---------------- pose RANSAC without an initial pose (map-wide relocalisation) ----------------
+ * Robust (pan, tilt, f) from n_corr >= 2 ray-pixel correspondences (rays [n_corr][2] in degrees, points
+ * [n_corr][2] in px), some of them wrong.  A pan/tilt/zoom camera's pose has a closed form from two
+ * correspondences i, j: f^2 from the angle between the two rays (a quadratic, up to two roots), then pan and tilt
+ * from correspondence i alone (two pan branches from one square root).  Sample h draws (i, j) from the stream of
+ * ptz_homography_ransac, keyed by (seed, h, draw), and owns the candidate slots 4 h + 2 root + branch (root 0: the
+ * quadratic's -(B + sgn(B) sqrt(disc)) / 2A root, root 1: the other; branch 0: the '+' square root of the pan
+ * equation, branch 1: the '-' one).  Every candidate is scored; a correspondence is an inlier when it lies in front
+ * of the camera and its reprojection error is < threshold px.  The winner has the most inliers; ties go to the
+ * lowest slot number (lowest sample, then the order above).  The winner is refitted by the LM of ptz_refine_poses
+ * (linear loss; ftol, xtol, max_iter) on its inliers, and the mask and count are taken at the refined pose.
+ *
+ * Outputs (any may be NULL): ptz_out[3] and cost_out (0.5 sum r^2 over the winner's inliers at the refined pose),
+ * ptz_hyp_out[3] the winner before the refit, best_sample_out its sample (-1: no sample gave a candidate),
+ * hyp_inliers_out its inlier count, mask_out[n_corr] (1 = inlier) and n_inliers_out at the refined pose,
+ * status_out 0 found / 1 not found.  Not found = the winner has fewer than min_inliers inliers (values below 3 are
+ * taken as 3: a two-point sample always explains its own two correspondences): ptz_out and cost_out are left
+ * untouched, mask_out is zeroed, n_inliers_out = 0; the winner outputs are still written when a candidate exists.
+ * One of the stateless front-end entry points (per-device work buffers and lock, see below).  opts NULL = defaults. */
+typedef struct {
+    int32_t n_hyp;        /* samples; default 1024 */
+    int32_t min_inliers;  /* default 3 */
+    int32_t max_iter;     /* refit LM, default 100 */
+    int32_t reserved;     /* 0 */
+    double threshold;     /* px, default 3.0 */
+    double ftol, xtol;    /* refit LM, defaults 1e-4 / 1e-8 */
+    uint64_t seed;
+} ptz_pose_ransac_opts;
+PTZBA_EXPORT int ptz_pose_ransac(int device, int64_t n_corr, const double* rays, const double* points, double u,
+                                 double v, const ptz_pose_ransac_opts* opts, double* ptz_out /*3*/,
+                                 double* ptz_hyp_out /*3, winner before refit*/, int32_t* best_sample_out,
+                                 int32_t* hyp_inliers_out, uint8_t* mask_out /*n_corr*/, int32_t* n_inliers_out,
+                                 double* cost_out, int32_t* status_out /*0 found, 1 not found*/);
+
 /* ---------------- host bookkeeping (native) ---------------- */
 /* ---------------- feature front-end (image_process.py:178-234, 418-441) ----------------
  * Stateless, synchronous entry points (no handle).  They keep per-device work buffers across calls and hold

@@ -26,6 +26,7 @@
 #include "../../include/ptzba.h"
 #include "host_util.h"
 #include "ptzba_common.h"
+#include "ransac_sample.h"
 
 namespace ptzba {
 
@@ -234,17 +235,7 @@ __global__ __launch_bounds__(256) void k_knn2_mf(int n1, int n2, const float* __
 // ---------------------------------------------------------------------------------------------
 // homography RANSAC
 // ---------------------------------------------------------------------------------------------
-__device__ __host__ inline uint64_t mix64(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// draw k of hypothesis h: a function of (seed, h, k, attempt) only
-__device__ __host__ inline uint32_t ransac_draw(uint64_t seed, uint32_t h, uint32_t k, uint32_t attempt, uint32_t n) {
-  const uint64_t z = mix64(seed * 0x9E3779B97F4A7C15ull + ((uint64_t)h << 20) + ((uint64_t)attempt << 4) + k + 1);
-  return (uint32_t)(z % n);
-}
-
+// (the sampling stream, ransac_draw, is ransac_sample.h: the pose RANSAC draws from it too)
 struct Norm {
   double c1x, c1y, s1, c2x, c2y, s2;  // p' = s (p - c)
 };

@@ -41,6 +41,11 @@ class ptz_refine_opts(Structure):
                 ("f_scale", c_double)]
 
 
+class ptz_pose_ransac_opts(Structure):
+    _fields_ = [("n_hyp", c_int32), ("min_inliers", c_int32), ("max_iter", c_int32), ("reserved", c_int32),
+                ("threshold", c_double), ("ftol", c_double), ("xtol", c_double), ("seed", ctypes.c_uint64)]
+
+
 class ptzba_lm_opts(Structure):
     _fields_ = [("ftol", c_double), ("xtol", c_double), ("gtol", c_double), ("lambda0", c_double),
                 ("min_lambda", c_double), ("max_lambda", c_double), ("max_iter", c_int32), ("max_retries", c_int32),
@@ -168,6 +173,8 @@ def lib():
         "ptz_keyframe_feature_counts": ([I32, I64, V, V, V, V, V, V], I),
         "ptz_pack_records": ([I32, I64, V, V, V, V, V, V, V, I64, V, V, V, V], I),
         "ptz_refine_poses": ([I, I32, V, I64, V, V, D, D, V, V, POINTER(ptz_refine_opts), V, V, V], I),
+        "ptz_pose_ransac": ([I, I64, V, V, D, D, POINTER(ptz_pose_ransac_opts), V, V, POINTER(c_int32), POINTER(c_int32),
+                            V, POINTER(c_int32), POINTER(c_double), POINTER(c_int32)], I),
         "ptz_corner_min_eig": ([I, I32, I32, V, V, V], I),
         "ptzba_partition_landmarks": ([I32, I32, I64, V, V, I32, I32, V, POINTER(c_int32), V], I),
         "ptzba_set_exchange_hook": ([V, EXCHANGE_FN, V], I),
@@ -222,7 +229,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_dist_info", "ptzba_owned_frames", "ptz_corner_min_eig", "ptz_orb", "ptzba_plan_summary",
     "ptzba_plan_export", "ptzba_dist_exchanges", "ptzba_dist_groups", "ptzba_exchange_group", "ptzba_dist_plan_summary",
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
-    "ptz_keyframe_feature_counts", "ptz_match_sets_ransac",
+    "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac",
 ]
 
 
@@ -556,6 +563,48 @@ def refine_poses(u, v, init_ptz, rays, points, subsets=None, ftol=1e-4, xtol=1e-
                                   float(v), _ptr(off), _ptr(idx), ctypes.byref(opts), _ptr(cost), _ptr(its), _ptr(st)),
            "ptz_refine_poses")
     return ptz, cost, its, st
+
+
+class PoseRansacResult:
+    """pose_ransac's result: ptz [3] (None when not found), ptz_hyp [3] the winning candidate before the refit (None
+    when no sample gave a candidate), best_sample, hyp_inliers, mask [n] bool, n_inliers, cost (None when not found),
+    found."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return ("PoseRansacResult(found=%s, ptz=%s, n_inliers=%d, ptz_hyp=%s, best_sample=%d, hyp_inliers=%d, cost=%s)"
+                % (self.found, self.ptz, self.n_inliers, self.ptz_hyp, self.best_sample, self.hyp_inliers, self.cost))
+
+
+def pose_ransac(u, v, rays, points, threshold=3.0, n_hyp=1024, seed=0, min_inliers=3, ftol=1e-4, xtol=1e-8,
+                max_iter=100, device=None):
+    """Robust (pan, tilt, f) from ray-pixel correspondences without an initial pose (ptz_pose_ransac): n_hyp two-point
+    samples, each giving up to four closed-form pose candidates, all scored against every correspondence (inlier:
+    in front of the camera, reprojection error < threshold px); the candidate with the most inliers (ties: lowest
+    sample, then candidate order) is refitted by the pose-only LM on its inliers.  rays / points [n, 2], n >= 2.
+    min_inliers below 3 is taken as 3.  Returns a PoseRansacResult."""
+    rays = _f64(rays).reshape(-1, 2)
+    points = _f64(points).reshape(-1, 2)
+    if len(rays) != len(points):
+        raise ValueError("rays and points differ in length")
+    n = len(rays)
+    opts = ptz_pose_ransac_opts(int(n_hyp), int(min_inliers), int(max_iter), 0, float(threshold), float(ftol),
+                                float(xtol), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    ptz = np.full(3, np.nan)
+    hyp = np.full(3, np.nan)
+    mask = np.zeros(max(n, 1), np.uint8)
+    best, hin, nin, st = c_int32(-1), c_int32(0), c_int32(0), c_int32(1)
+    cost = c_double(np.nan)
+    _check(lib().ptz_pose_ransac(default_device() if device is None else int(device), n, _ptr(rays), _ptr(points),
+                                 float(u), float(v), ctypes.byref(opts), _ptr(ptz), _ptr(hyp), ctypes.byref(best),
+                                 ctypes.byref(hin), _ptr(mask), ctypes.byref(nin), ctypes.byref(cost),
+                                 ctypes.byref(st)), "ptz_pose_ransac")
+    found = st.value == 0
+    return PoseRansacResult(ptz=ptz if found else None, ptz_hyp=hyp if best.value >= 0 else None,
+                            best_sample=int(best.value), hyp_inliers=int(hin.value), mask=mask[:n].astype(bool),
+                            n_inliers=int(nin.value), cost=float(cost.value) if found else None, found=found)
 
 
 def build_landmarks_flat(kp_count, pair_i, pair_j, pair_count, idx_a, idx_b):

@@ -3,8 +3,10 @@ Map of keyframes and global ray landmarks (reference: slam_system/scene_map.py:1
 
 `Map.add_keyframe_with_ba` re-runs bundle adjustment over all keyframes, as the reference does
 (scene_map.py:53-117), on the GPU.  `RandomForestMap` keeps the reference's sliding-window BA
-(`bundle_adjustment_processing`, last `max_ba_frame` keyframes, scene_map.py:198-244); its random-forest
-relocaliser (C++ rf_map via ctypes) is out of scope and raises if used.
+(`bundle_adjustment_processing`, last `max_ba_frame` keyframes, scene_map.py:198-244).  The reference's
+random-forest relocaliser (C++ rf_map via ctypes) is out of scope; `RandomForestMap.relocalize`
+answers the same call with the nearest-neighbour ray map of nearest_neighbor.py and the two-point pose RANSAC
+(ptzba.pose_ransac) in its place.
 
 Both keep a correspondence.CorrespondenceCache keyed by KeyFrame.img_index: the reference re-detects
 every keyframe and re-matches every pair on each BA call; here only the new keyframe is detected and
@@ -106,7 +108,10 @@ class Map:
 class RandomForestMap:
     """Sliding-window BA of scene_map.py:171-244: the last `max_ba_frame` keyframes are adjusted (the first
     of them is the gauge, bundle_adjustment fixes frame 0), older keyframes are kept as they are.  The
-    random-forest map files / relocaliser (rf_map, C++) are not part of this build."""
+    random-forest map files (rf_map, C++) are not part of this build: `relocalize` searches a nearest-neighbour
+    descriptor -> ray database over the keyframes (nearest_neighbor.NNBasedMap, exact kNN on the GPU) where the
+    reference walks its forest, and estimates the pose from the matches by the two-point PTZ pose RANSAC where the
+    reference runs its preemptive RANSAC (rf_map/util/ptz_pose_estimation.cpp)."""
 
     def __init__(self, max_ba_frame=10, feature_method="sift", cache_correspondences=True):
         self.keyframe_list = []
@@ -115,9 +120,12 @@ class RandomForestMap:
         self.global_ray = np.ndarray([0, 2])
         self.ba_options = {}
         self.correspondences = CorrespondenceCache() if cache_correspondences else None
+        self.reloc_options = {}  # threshold / n_hyp / seed of relocalize's pose RANSAC
+        self._nn_map = None  # the descriptor -> ray database of relocalize, rebuilt after add_keyframe
 
     def add_keyframe(self, keyframe):
         self.keyframe_list.append(keyframe)
+        self._drop_nn_map()
         if len(self.keyframe_list) > 1:
             self.bundle_adjustment_processing()
 
@@ -144,5 +152,17 @@ class RandomForestMap:
                 print("warning: key frame, %d, image index %d is not included in the map" % (i, idx[i]))
         return landmarks, kfs
 
+    def _drop_nn_map(self):
+        if self._nn_map is not None:
+            self._nn_map.close()
+            self._nn_map = None
+
     def relocalize(self, keyframe, ptz):
-        raise NotImplementedError("random-forest relocalisation (C++ rf_map) is out of scope for this build")
+        """The camera pose [3] of `keyframe` (its feature_pts / feature_des; its own pose is not read) against the
+        keyframes of the map at their current, bundle-adjusted poses, or `ptz` when no pose is found."""
+        if self._nn_map is None:
+            from nearest_neighbor import NNBasedMap
+            self._nn_map = NNBasedMap()
+            self._nn_map.add_keyframes([k for k in self.keyframe_list if k.get_feature_num() > 0])
+        pose, n_inliers, found = self._nn_map.relocalize_robust(keyframe, **self.reloc_options)
+        return pose if found else np.asarray(ptz, np.float64)
