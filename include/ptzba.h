@@ -163,6 +163,11 @@ PTZBA_EXPORT int ptzba_problem_info(ptzba_handle h, int64_t* info8);
  * [2] workgroups whose landmarks' frame range exceeds the LDS frame table, so they read the tables from global memory,
  * [3] the largest number of segment windows one landmark is walked in */
 PTZBA_EXPORT int ptzba_k1_info(ptzba_handle h, int64_t* info4);
+/* the reduced-system kernel's work items (each runs its landmark list in batches of 16, two batches per round of
+ * its operand ring): [0] items, [1] chunk-0 items (they also sum the diagonal terms), [2] / [3] shortest / longest
+ * list, then how many items have [4] at most 16 landmarks (one batch), [5] nl % 32 in 1..16 (odd batch count),
+ * [6] nl % 32 in 17..31 (even count, ragged last batch), [7] nl % 32 == 0 */
+PTZBA_EXPORT int ptzba_k2_info(ptzba_handle h, int* info8);
 /* host phase times of the last ptzba_set_problem (sort, segments, K2 structure, plan, uploads ...): names[k] (static
  * strings) and ms[k] for k < min(cap, *n_out); *n_out = the number of phases recorded */
 PTZBA_EXPORT int ptzba_setup_timing(ptzba_handle h, int32_t cap, const char** names, double* ms, int32_t* n_out);

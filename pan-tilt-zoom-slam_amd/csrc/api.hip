@@ -65,6 +65,8 @@ struct ptzba_ctx {
   DBuf s2_items, s2_groups, s2_lm, lm_meta;  // K2 work items / tiles / lists, slot ranges
   DBuf s2_part, part_diag;                                    // K2 split partials (blocks, diagonal terms)
   int n_s2_items = 0, n_s2_groups = 0;
+  int k2_pipe = 1;     // fp32 K2 kernel: 1 producer / consumer waves (waves 0-3 stage), 2 (even waves stage), 0 k_schur_mf
+  int k2_info[8] = {};  // ptzba_k2_info
   int64_t n_slot = 0;  // dense landmark x frame slots (W table rows)
   // device: state
   DBuf ptz, rays, ptz_trial, rays_trial, D_pose, D_ray;
@@ -1734,6 +1736,23 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
     }
     h->n_s2_groups = (int)(s2_groups.size() / 4);
     h->n_s2_items = (int)(s2_items.size() / 4);
+    // which pipeline shapes the items run (ptzba_k2_info): batches of 16 landmarks, two per ring round trip
+    {
+      int* ki = h->k2_info;
+      for (int k = 0; k < 8; ++k) ki[k] = 0;
+      ki[0] = h->n_s2_items;
+      for (size_t k = 0; k < s2_items.size(); k += 4) {
+        const int nl = s2_items[k + 3] - s2_items[k + 2], m = nl % 32;
+        if (s2_items[k + 1] == 0) ++ki[1];
+        ki[2] = k == 0 ? nl : std::min(ki[2], nl);
+        ki[3] = std::max(ki[3], nl);
+        if (nl <= 16) ++ki[4];
+        ++ki[m == 0 ? 7 : (m <= 16 ? 5 : 6)];
+      }
+    }
+    // PTZBA_K2_PIPE=0: the block-synchronous k_schur_mf (kept for one round: A/B and the bitwise parity test);
+    // =even: the even waves stage instead of waves 0-3
+    h->k2_pipe = getenv_is("PTZBA_K2_PIPE", "0") ? 0 : (getenv_is("PTZBA_K2_PIPE", "even") ? 2 : 1);
     {
       std::vector<uint8_t> cov((n_pose + SCHUR_F1) / SCHUR_F1 + 1, 0);
       for (size_t g = 0; g < s2_groups.size(); g += 4)
@@ -2049,6 +2068,12 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
   return 0;
 }
 
+int ptzba_k2_info(ptzba_handle h, int* out) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  for (int k = 0; k < 8; ++k) out[k] = h->k2_info[k];
+  return 0;
+}
+
 int ptzba_k1_info(ptzba_handle h, int64_t* info) {
   if (!h || !h->have_problem) return fail("no problem set");
   info[0] = h->n_work;
@@ -2346,9 +2371,9 @@ static int build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   a.prep = fp;
   tm_begin(h, TM_SCHUR);
   if (h->precision == PTZBA_FP32)
-    launch_schur<float>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st);
+    launch_schur<float>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, h->k2_pipe);
   else
-    launch_schur<double>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st);
+    launch_schur<double>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, 0);
   tm_end(h, TM_SCHUR);
   HIPCHK(hipGetLastError());
   if (h->dist_mode) {

@@ -223,7 +223,7 @@ template <typename real>
 // start / end timestamps, no marker packets around it)
 void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 template <typename real>
-void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st);
+void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, int pipe);
 // scratch: RED_SCRATCH doubles (partials + counter), zero-initialised once, reused across calls
 constexpr int RED_SCRATCH = 64 * 8 + 2;
 // scal[8] | loc[8] | info -> one packed device block (read back with a single copy)

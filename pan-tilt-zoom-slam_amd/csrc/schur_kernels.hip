@@ -549,6 +549,8 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
     SK_NOW(skt);
     if (diag && p + SNB < nl) dfetch(p + SNB);
     fetch(A, p + 2 * SNB);
+    SK_ACC(11, skt);  // fetch issue (list reads, addresses, loads)
+    SK_NOW(skt);
     compute(0);
     SK_ACC(4, skt);
     SK_NOW(skt);
@@ -564,6 +566,8 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
     SK_NOW(skt);
     if (diag && p + 2 * SNB < nl) dfetch(p + 2 * SNB);
     fetch(B, p + 3 * SNB);
+    SK_ACC(11, skt);
+    SK_NOW(skt);
     compute(1);
     SK_ACC(4, skt);
     SK_NOW(skt);
@@ -604,6 +608,358 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
         out[(i * 9 + 3 * q + r) * WAVE + f2] = c[x][y][v] * back;
       }
   SK_T(10);
+#ifdef SK_TIMING
+  __syncthreads();
+  if (threadIdx.x == 0 && item < 4096) g_sk_items[item][1] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+
+// ------------------------------------------------------------------------------------------------
+// Producer / consumer form of k_schur_mf (the fp32 default; PTZBA_K2_PIPE=0 keeps k_schur_mf): the same
+// work items, operand layout, arithmetic and partials, but the eight waves take fixed roles so that the
+// staging of one batch (loads, g_l scaling, fp16 splits, LDS writes: VALU + memory issue) runs beside the
+// products of another (fragment reads + MFMAs) on every SIMD instead of before them:
+//   * 4 staging waves: what fetch / stage / dfetch / daccum of k_schur_mf do, each thread with twice the
+//     elements (four W slots, two (landmark, f1) pairs -- the same element -> LDS location map, and one
+//     dacc set per pair as before, so every sum keeps its order; which thread takes which element is
+//     free, see MF_WMAP); V~^-1, g_l and V~^-1 g come from a per-landmark LDS table built with the list;
+//   * 4 product waves: 18 output blocks each (3 row blocks x 6 column blocks), per block al*bh, ah*bl,
+//     ah*bh in batch order as before, then the partial store.
+// Hand-off: a ring of MF_RING operand buffers and two LDS counter sets, one counter per wave and one
+// writer per counter: s_ready[w] = b + 1 once staging wave w's part of batch b is in LDS (after
+// lgkmcnt(0)), s_done[w] = b + 1 once product wave w holds batch b's fragments in registers (after
+// lgkmcnt(0)).  A product wave starts batch b when all four s_ready >= b + 1; a staging wave re-fills the
+// buffer of batch b - MF_RING when all four s_done >= b - MF_RING + 1.
+// Why it cannot stall: the counters live in LDS and are zeroed before the one __syncthreads that precedes
+// every wait; the skip_if exit is taken by whole workgroups before it; the batch count nb is block-uniform,
+// so all eight waves run the same number of hand-offs; a counter only grows, and the wait of batch b on
+// either side needs only signals of batches < b from the other side (s_ready of b needs s_done of
+// b - MF_RING, which needs s_ready of b - MF_RING): the dependency chain ends at batch 0, which waits for
+// nothing.  No wait looks at global memory or at another workgroup.
+// ------------------------------------------------------------------------------------------------
+#ifndef MF_RING
+#define MF_RING 2  // operand buffers in the ring (2: 116 KB of LDS; 3: 159 KB, measured no faster)
+#endif
+#ifndef MF_STAGGER
+#define MF_STAGGER 0
+#endif
+#ifndef MF_WMAP
+#define MF_WMAP 1
+#endif
+__device__ __forceinline__ void k2_signal(int* p, int v) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores / fragment reads are done
+  if (lane_id() == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// all four counters of a set >= v (v <= 0: nothing to wait for)
+__device__ __forceinline__ void k2_wait4(const int* p, int v) {
+  if (v > 0) {
+    for (;;) {
+      const int c0 = __hip_atomic_load(p + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const int c1 = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const int c2 = __hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const int c3 = __hip_atomic_load(p + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (__builtin_amdgcn_readfirstlane(min(min(c0, c1), min(c2, c3))) >= v) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+  }
+  asm volatile("" ::: "memory");
+}
+
+// EVEN: the even waves stage (else waves 0-3)
+template <bool EVEN>
+__global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
+  constexpr int SNB = 16;                // landmarks per batch
+  constexpr int NR = MF_RING;
+  constexpr int NSL = SNB * WAVE / 256;  // W slots staged per staging thread per batch
+  constexpr int NYP = SNB * SF / 256;    // (landmark, f1) pairs per staging thread per batch
+  __shared__ __attribute__((aligned(16))) _Float16 sY[NR][2][3 * SF][MKP];     // [buf][hi|lo][q*32 + f1][2j + d]
+  __shared__ __attribute__((aligned(16))) _Float16 sWt[NR][2][3 * WAVE][MKP];  // [buf][hi|lo][r*64 + f2][2j + d]
+  __shared__ int4 sL[SCHUR_LMAX];
+  // per landmark of the list, converted once instead of per (landmark, f1) pair: {V~^-1 (3, fp32), 1 / g_l} and
+  // {g_l, V~^-1 g (2, fp32: the diagonal terms' factor), -}
+  __shared__ float4 sV[SCHUR_LMAX], sD[SCHUR_LMAX];
+  __shared__ int s_ready[4], s_done[4];
+  static_assert(sizeof(sWt) >= 512 * 12 * sizeof(double), "the diagonal terms' reduction reuses sWt");
+  if (a.skip_if && *a.skip_if) return;
+  const int t = threadIdx.x, lane = lane_id(), wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const bool prod = EVEN ? !(wv & 1) : wv < 4;
+  const int rk = EVEN ? wv >> 1 : wv & 3;  // rank inside the role
+#ifdef SK_TIMING
+  const bool skrec = lane == 0 && rk == 0 && blockIdx.x < 16;  // first staging and first product wave
+  long long* sk = g_sk[blockIdx.x & 15];
+  if (skrec && prod)
+    for (int k = 0; k < 16; ++k) sk[k] = 0;
+  long long tk0 = 0, tk1 = 0, tk2 = 0;
+#define SKP_ACC(v, t0) do { if (skrec) v += clock64() - (t0); } while (0)
+#else
+#define SKP_ACC(v, t0) do { } while (0)
+#endif
+  long long skt = 0;
+  (void)skt;
+  if (prod) SK_T(0);
+  const int item = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int4 it = a.items[item];
+#ifdef SK_TIMING
+  if (threadIdx.x == 0 && item < 4096) {
+    g_sk_items[item][0] = __builtin_amdgcn_s_memrealtime();
+    g_sk_items[item][2] = it.y;
+    g_sk_items[item][3] = it.w - it.z;
+  }
+#endif
+  const int f1b = it.x, chunk = it.y, lb = it.z, nl = it.w - it.z;
+  const int nb = (nl + SNB - 1) / SNB;  // batches (block-uniform)
+  const int f2base = f1b + WAVE * chunk;
+  const bool alt = a.sel && *a.sel;  // device-chosen linearisation slot
+  const float* __restrict__ w_slot = (const float*)(alt ? a.w_slot1 : a.w_slot);
+  for (int k = t; k < nl; k += 512) {
+    const int4 m = a.item_lm[lb + k];
+    sL[k] = m;
+    const double* vi = a.lm_aux + (int64_t)m.x * 8;
+    int e = 0;
+    (void)frexp(vi[0] + vi[2], &e);
+    const float g = ldexpf(1.f, e / 2);
+    sV[k] = make_float4((float)vi[0], (float)vi[1], (float)vi[2], 1.f / g);  // (1 / g: a power of two, exact)
+    sD[k] = make_float4(g, (float)vi[3], (float)vi[4], 0.f);
+  }
+  if (t < 4) {
+    s_ready[t] = 0;
+    s_done[t] = 0;
+  }
+  __syncthreads();
+  if (prod) SK_T(1);
+
+  if (prod) {
+    // ---- staging waves ----
+    const int pt = rk * WAVE + lane;  // 0..255
+    const bool diag = chunk == 0;
+    const float* __restrict__ ug_slot = (const float*)(alt ? a.ug_slot1 : a.ug_slot);
+    // staging registers of one batch (two sets: the loads of batch b + 2 are issued when batch b is staged)
+    struct Pre {
+      float rw[NSL][6], rgw[NSL], ryw[NYP][6];
+      float4 rv[NYP];  // V~^-1 | 1 / g
+      bool rwin[NSL], ryin[NYP];
+      float du[NYP][9], dg[NYP][2];
+    };
+    // element map of a staging thread: W slot q -> (landmark j of the batch, frame ln of the chunk), pair u ->
+    // (landmark yj, frame yi of F1).  Any bijection gives the same LDS contents and the same sums (one dacc set per
+    // pair).  MF_WMAP 0: k_schur_mf's order (a wave = 64 consecutive frames of one landmark; its b32 LDS stores hit
+    // rows 80 B apart: 16 banks, 4-way conflicts); 1: a wave = 16 consecutive frames x 4 landmarks, whose stores
+    // (bank = 20 frame + landmark mod 64) reach all 64 banks; a landmark's loads still run over 16 consecutive slots
+    // (384 B).
+#if MF_WMAP
+    auto wj = [&](int) { return (lane >> 4) + 4 * rk; };
+    auto wln = [&](int q) { return (lane & 15) + 16 * q; };
+    auto pyj = [&](int) { return (lane >> 4) + 4 * rk; };
+    auto pyi = [&](int u) { return (lane & 15) + 16 * u; };
+#else
+    auto wj = [&](int q) { return (pt + 256 * q) >> 6; };
+    auto wln = [&](int q) { return (pt + 256 * q) & 63; };
+    auto pyj = [&](int u) { return pt / SF + (256 / SF) * u; };
+    auto pyi = [&](int) { return pt & (SF - 1); };
+#endif
+    auto fetch = [&](Pre& P, int p) {  // landmarks [p, p + SNB) of the list (clamped, branch-free)
+#pragma unroll
+      for (int q = 0; q < NSL; ++q) {
+        const int j = wj(q), ln = wln(q);
+        const int jj = min(p + j, nl - 1);
+        const int4 m = sL[jj];
+        const int idx = f2base + ln - m.y;
+        P.rwin[q] = (p + j < nl) && idx >= 0 && f2base + ln <= m.z;
+        P.rgw[q] = sD[jj].x;
+        slot_load6(P.rw[q], w_slot + (int64_t)(m.w + min(max(idx, 0), m.z - m.y)) * W_STRIDE);
+      }
+#pragma unroll
+      for (int u = 0; u < NYP; ++u) {
+        const int yj = pyj(u), yi = pyi(u);
+        const int f = f1b + yi, jj = min(p + yj, nl - 1);
+        const int4 m = sL[jj];
+        P.ryin[u] = (p + yj < nl) && f >= m.y && f <= m.z;
+        P.rv[u] = sV[jj];
+        const int64_t slot = m.w + min(max(f - m.y, 0), m.z - m.y);
+        slot_load6(P.ryw[u], w_slot + slot * W_STRIDE);
+        if (diag && p < nl) {  // chunk-0 items: the pair's U | g_pose terms (block-uniform branch)
+          slot_load9(P.du[u], ug_slot + slot * UG_STRIDE);
+          P.dg[u][0] = sD[jj].y;
+          P.dg[u][1] = sD[jj].z;
+        }
+      }
+    };
+    auto stage = [&](const Pre& P, int buf) {
+#pragma unroll
+      for (int q = 0; q < NSL; ++q) {
+        const int j = wj(q), ln = wln(q);
+        const float gq = P.rwin[q] ? P.rgw[q] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          hp2v h, l;
+          const float gr = r == 2 ? gq * MF_FROW : gq;
+          split_pk(P.rw[q][2 * r] * gr, P.rw[q][2 * r + 1] * gr, h, l);
+          *reinterpret_cast<hp2v*>(&sWt[buf][0][r * WAVE + ln][2 * j]) = h;
+          *reinterpret_cast<hp2v*>(&sWt[buf][1][r * WAVE + ln][2 * j]) = l;
+        }
+      }
+      // Y / g = -(W / g) V~^-1, staged negated (as k_schur_mf)
+#pragma unroll
+      for (int u = 0; u < NYP; ++u) {
+        const int yj = pyj(u), yi = pyi(u);
+        const float gi = P.ryin[u] ? P.rv[u].w : 0.f;
+        const float v0 = P.rv[u].x * gi, v1 = P.rv[u].y * gi, v2 = P.rv[u].z * gi;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          const float W0 = P.ryw[u][2 * q], W1 = P.ryw[u][2 * q + 1];
+          hp2v h, l;
+          const float sq = q == 2 ? -MF_FROW : -1.f;
+          split_pk(sq * fmaf(W0, v0, W1 * v1), sq * fmaf(W0, v1, W1 * v2), h, l);
+          *reinterpret_cast<hp2v*>(&sY[buf][0][q * SF + yi][2 * yj]) = h;
+          *reinterpret_cast<hp2v*>(&sY[buf][1][q * SF + yi][2 * yj]) = l;
+        }
+      }
+    };
+    float dacc[NYP][12];  // fp32 over the item's <= 32 batches, one set per pair (as k_schur_mf)
+#pragma unroll
+    for (int u = 0; u < NYP; ++u)
+#pragma unroll
+      for (int k = 0; k < 12; ++k) dacc[u][k] = 0.f;
+    auto daccum = [&](const Pre& P) {
+#pragma unroll
+      for (int u = 0; u < NYP; ++u)
+        if (P.ryin[u]) {
+          const float g0 = P.dg[u][0], g1 = P.dg[u][1];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) dacc[u][k] += P.du[u][k];
+#pragma unroll
+          for (int q = 0; q < 3; ++q) dacc[u][9 + q] += fmaf(P.ryw[u][2 * q], g0, P.ryw[u][2 * q + 1] * g1);
+        }
+    };
+    Pre A, B;
+#if MF_STAGGER
+    // the four staging waves start MF_STAGGER * 64 cycles apart, so that their load bursts do not meet in the CU's
+    // one address path (they do the same work per batch and keep the offset)
+    for (int k = 0; k < rk; ++k) __builtin_amdgcn_s_sleep(MF_STAGGER);
+#endif
+    if (nb > 0) {
+      fetch(A, 0);
+      // (keeps set A's loads ahead of set B's in issue order, as in the loop: interleaved here, the loop's first
+      // stage(A) would have to wait for B's loads too)
+      __builtin_amdgcn_sched_barrier(0);
+      fetch(B, SNB);
+    }
+    SK_T(2);
+    SK_T(3);
+#ifdef SK_TIMING
+    if (skrec) {
+      sk[8] = nl;
+      sk[9] = chunk;
+    }
+#endif
+    // batch b from set A (b even) or B (b odd) into buffer b % NR.  The loop always runs both halves and has one
+    // exit (an odd last batch is staged after it): with a second exit between the halves the compiler's wait
+    // counts at the loop head must allow for set A's loads being the newest, and stage(A) waits for set B's too.
+    int buf = 0;
+    auto half = [&](Pre& P, int b, bool again) {
+      SK_NOW(skt);
+      k2_wait4(s_done, b - NR + 1);
+      SKP_ACC(tk0, skt);
+      SK_NOW(skt);
+      stage(P, buf);
+      if (diag) daccum(P);
+      k2_signal(&s_ready[rk], b + 1);
+      SKP_ACC(tk1, skt);
+      SK_NOW(skt);
+      if (again) fetch(P, (b + 2) * SNB);
+      SKP_ACC(tk2, skt);
+      buf = buf + 1 == NR ? 0 : buf + 1;
+    };
+    int b = 0;
+    for (; b + 1 < nb; b += 2) {
+      half(A, b, true);
+      half(B, b + 1, true);
+    }
+    if (b < nb) half(A, b, false);
+    SK_T(7);
+#ifdef SK_TIMING
+    if (skrec) {
+      sk[6] = tk0;
+      sk[5] = tk1;
+      sk[11] = tk2;
+    }
+#endif
+    if (diag) {  // fixed-order reduction over the 16 landmark lanes of each frame (as k_schur_mf)
+      k2_wait4(s_done, nb);  // the last fragment reads of the ring have landed: sWt is free
+      double* red = reinterpret_cast<double*>(&sWt[0][0][0][0]);
+#pragma unroll
+      for (int u = 0; u < NYP; ++u)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) red[(pyj(u) * SF + pyi(u)) * 12 + k] = (double)dacc[u][k];
+      k2_signal(&s_ready[rk], nb + 1);
+      k2_wait4(s_ready, nb + 1);  // all four staging waves' terms are in `red`
+      for (int e = pt; e < SF * 12; e += 256) {
+        double v = 0;
+        for (int j0 = 0; j0 < 512 / SF; ++j0) v += red[j0 * SF * 12 + e];
+        a.part_diag[(int64_t)item * SF * 12 + e] = v;
+      }
+    }
+    SK_T(10);
+  } else {
+    // ---- product waves: row blocks 3 rg.., column blocks 6 cg.. ----
+    const int rg = rk >> 1, cg = rk & 1;
+    const int fr = lane & 15, fk = (lane >> 4) * 8;  // fragment row / column and k offset of this lane
+    f4v c[3][6];  // fp32 over all the item's batches (see k_schur_mf)
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = 0; y < 6; ++y) c[x][y] = f4v{0.f, 0.f, 0.f, 0.f};
+    int buf = 0;
+    for (int b = 0; b < nb; ++b) {
+      SK_NOW(skt);
+      k2_wait4(s_ready, b + 1);
+      SKP_ACC(tk0, skt);
+      SK_NOW(skt);
+      h8v bh[6], bl[6], ah[3], al[3];
+#pragma unroll
+      for (int y = 0; y < 6; ++y) {
+        const int col = 16 * (6 * cg + y) + fr;
+        bh[y] = *reinterpret_cast<const h8v*>(&sWt[buf][0][col][fk]);
+        bl[y] = *reinterpret_cast<const h8v*>(&sWt[buf][1][col][fk]);
+      }
+#pragma unroll
+      for (int x = 0; x < 3; ++x) {
+        const int row = 16 * (3 * rg + x) + fr;
+        ah[x] = *reinterpret_cast<const h8v*>(&sY[buf][0][row][fk]);
+        al[x] = *reinterpret_cast<const h8v*>(&sY[buf][1][row][fk]);
+      }
+      k2_signal(&s_done[rk], b + 1);  // the fragments are in registers: the buffer may be re-filled
+#pragma unroll
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 6; ++y) {
+          c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[x], bh[y], c[x][y], 0, 0, 0);
+          c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[x], bl[y], c[x][y], 0, 0, 0);
+          c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[x], bh[y], c[x][y], 0, 0, 0);
+        }
+      SKP_ACC(tk1, skt);
+      buf = buf + 1 == NR ? 0 : buf + 1;
+    }
+#ifdef SK_TIMING
+    if (skrec) {
+      sk[12] = tk0;
+      sk[4] = tk1;
+    }
+#endif
+    // partial blocks of this split: part[item][f1 local][3q + r][f2], as k_schur writes them
+    float* out = (float*)a.part + (int64_t)item * (SF * 9 * WAVE);
+#pragma unroll
+    for (int x = 0; x < 3; ++x)
+#pragma unroll
+      for (int y = 0; y < 6; ++y)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int row = 16 * (3 * rg + x) + (lane >> 4) * 4 + v, col = 16 * (6 * cg + y) + fr;
+          const int q = row / SF, i = row % SF, r = col / WAVE, f2 = col % WAVE;
+          const float back = (q == 2 ? 1.f / MF_FROW : 1.f) * (r == 2 ? 1.f / MF_FROW : 1.f);  // (exact: powers of two)
+          out[(i * 9 + 3 * q + r) * WAVE + f2] = c[x][y][v] * back;
+        }
+  }
 #ifdef SK_TIMING
   __syncthreads();
   if (threadIdx.x == 0 && item < 4096) g_sk_items[item][1] = __builtin_amdgcn_s_memrealtime();
@@ -716,12 +1072,15 @@ __global__ __launch_bounds__(256) void k_schur_reduce(SchurArgs a) {
 }
 
 template <typename real>
-void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st) {
+void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, int pipe) {
   const int n_free = a.n_pose - n_fixed;
   if (n_free <= 0) return;
-  // fp32: the matrix cores (k_schur_mf, fp16 hi/lo splits); fp64: the VALU kernel
+  // fp32: the matrix cores (fp16 hi/lo splits; pipe 1 / 2: the producer / consumer form with waves 0-3 / the even
+  // waves staging, 0: k_schur_mf); fp64: the VALU kernel
   if (n_items > 0) {
-    if (sizeof(real) == 4) hipLaunchKernelGGL(k_schur_mf, dim3(n_items), dim3(512), 0, st, a);
+    if (sizeof(real) == 4 && pipe == 1) hipLaunchKernelGGL(k_schur_mfp<false>, dim3(n_items), dim3(512), 0, st, a);
+    else if (sizeof(real) == 4 && pipe == 2) hipLaunchKernelGGL(k_schur_mfp<true>, dim3(n_items), dim3(512), 0, st, a);
+    else if (sizeof(real) == 4) hipLaunchKernelGGL(k_schur_mf, dim3(n_items), dim3(512), 0, st, a);
     else hipLaunchKernelGGL(k_schur<real>, dim3(n_items), dim3(512), 0, st, a);
   }
   if (n_groups > 0)
@@ -729,7 +1088,7 @@ void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hi
                        dim3(256), 0, st, a);
 }
 
-template void launch_schur<float>(const SchurArgs&, int, int, int, hipStream_t);
-template void launch_schur<double>(const SchurArgs&, int, int, int, hipStream_t);
+template void launch_schur<float>(const SchurArgs&, int, int, int, hipStream_t, int);
+template void launch_schur<double>(const SchurArgs&, int, int, int, hipStream_t, int);
 
 }  // namespace ptzba

@@ -115,6 +115,7 @@ def lib():
         "ptzba_set_problem": ([V, I32, I32, I64, V, V, V, V, D, D, POINTER(ptzba_problem_opts)], I),
         "ptzba_problem_info": ([V, V], I),
         "ptzba_k1_info": ([V, V], I),
+        "ptzba_k2_info": ([V, V], I),
         "ptzba_solver_info": ([V, V], I),
         "ptzba_residual": ([V, V, V], I),
         "ptzba_set_state": ([V, V, V], I),
@@ -216,7 +217,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "ptzba_new", "ptzba_delete", "ptzba_last_error", "ptzba_version", "ptzba_set_stream", "ptzba_use_own_stream", "ptzba_set_problem",
-    "ptzba_problem_info", "ptzba_k1_info", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
+    "ptzba_problem_info", "ptzba_k1_info", "ptzba_k2_info", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
     "ptzba_build_reduced", "ptzba_solve_reduced", "ptzba_step", "ptzba_set_huber_curvature", "ptzba_set_setup_front", "ptzba_setup_timing", "ptzba_solve", "ptzba_solve_resident", "ptzba_read_scalars", "ptzba_accept",
     "ptzba_lm_start", "ptzba_lm_init", "ptzba_lm_build", "ptzba_lm_solve", "ptzba_lm_decide", "ptzba_lm_wait",
     "ptzba_exchange", "ptzba_exchange_packed", "ptzba_pack", "ptzba_unpack", "ptzba_sync", "ptzba_kernel_times", "ptzba_reset_kernel_times", "ptzba_comm_times", "ptzba_dist_form_estimate", "ptzba_save_state", "ptzba_restore_state", "ptz_ray_to_image",
@@ -1074,6 +1075,14 @@ class BAHandle:
         out = np.zeros(4, np.int64)
         _check(lib().ptzba_k1_info(self.h, _ptr(out)), "ptzba_k1_info")
         return [int(x) for x in out]
+
+    def k2_info(self):
+        """The reduced-system kernel's work items (ptzba_k2_info): items, chunk-0 items, shortest / longest landmark
+        list, and the items with at most 16 landmarks, with nl % 32 in 1..16, in 17..31, and == 0."""
+        out = np.zeros(8, np.int32)
+        _check(lib().ptzba_k2_info(self.h, _ptr(out)), "ptzba_k2_info")
+        keys = ["items", "chunk0_items", "nl_min", "nl_max", "nl_le16", "nl_mod32_1_16", "nl_mod32_17_31", "nl_mod32_0"]
+        return dict(zip(keys, [int(x) for x in out]))
 
     def residual(self, x_full):
         x_full = _f64(x_full, (-1,))

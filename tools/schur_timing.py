@@ -1,5 +1,8 @@
 """Phase timing of K2 (k_schur) from a -DSK_TIMING build (PTZBA_LIB): clock64 stamps of thread 0 of the
-first 16 workgroups: [list load, diag phase, first stage, batches: compute / stage / barrier sums, tail]."""
+first 16 workgroups: [list load, diag phase, first stage, batches: fetch / compute / stage / barrier sums, tail].
+Producer / consumer kernel (the default): fetch, stage and "barrier" (the wait for a free ring buffer) are the first
+staging wave's, compute and cwait (the wait for a staged batch) the first product wave's; PTZBA_K2_PIPE=0 times
+k_schur_mf, whose phases are all thread 0's."""
 import ctypes
 import os
 import sys
@@ -26,7 +29,7 @@ assert L.ptzba_debug_sk(buf.ctypes.data) == 0
 for b in range(16):
     r = buf[b]
     print(f"wg {b:2d} nl {r[8]:4d} chunk {r[9]} | list {r[1]-r[0]:6d} diag {r[2]-r[1]:6d} stage0 {r[3]-r[2]:6d} | "
-          f"compute {r[4]:7d} stage {r[5]:7d} barrier {r[6]:7d} | write {r[10]-r[7]:6d} | total {r[10]-r[0]:7d}")
+          f"fetch {r[11]:7d} compute {r[4]:7d} cwait {r[12]:7d} stage {r[5]:7d} barrier {r[6]:7d} | write {r[10]-r[7]:6d} | total {r[10]-r[0]:7d}")
 
 # per-item start / end (s_memrealtime, 10 ns ticks): occupancy of the launch and the tail
 L.ptzba_debug_sk_items.argtypes = [ctypes.c_void_p]
