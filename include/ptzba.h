@@ -262,6 +262,29 @@ PTZBA_EXPORT int ptzba_solve_resident(ptzba_handle h, int restore, const ptzba_l
 /* host-driven LM (ptzba_linearize / ptzba_step): the huber curvature weight (in (0, 1], units of rho' beyond the
  * unit) of the following linearisations; set_problem resets it to 1 (IRLS) */
 PTZBA_EXPORT int ptzba_set_huber_curvature(ptzba_handle h, double hc);
+/* Posterior covariance at the handle's current state (ptzba_version 0.3): the diagonal blocks of scale * H^-1, H the
+ * undamped Gauss-Newton normal matrix J^T diag(rho') J over the free parameters [3 (n_pose - n_fixed) poses | rays]
+ * (huber: the IRLS weights, whatever curvature the LM last used).  pose_cov [n_pose][3][3] (pan, tilt, f; the fixed
+ * frames' blocks all zero; may be NULL), ray_cov [n][2][2] of the landmarks lm_index[0 .. n_lm) (duplicates allowed;
+ * n_lm = -1: every landmark in order, lm_index ignored; may be NULL when n_lm == 0; a landmark without records gets a
+ * zero block).  info [4] (may be NULL): the scale used, the smallest pivot of the reduced system's Cholesky factor,
+ * the number of free parameters, milliseconds on the device.
+ * A between-solves call (no LM trial pending): it linearises the current state, builds and factors the reduced system
+ * at lambda = 0 and runs the selected inverse on the handle's stream, then leaves the handle as ptzba_linearize does.
+ * The Marquardt scales and the huber curvature setting are put back, so a solve started afterwards takes bitwise the
+ * steps it takes without the call.  Single rank only: a sharded handle, or one with a communicator or hook attached,
+ * is refused.  Fails (nothing written to the output buffers) when the undamped system is not positive definite, e.g.
+ * when a free frame has no observation.
+ * ABI: struct_size must be sizeof(ptzba_cov_opts) of the header the caller was compiled with; a size this library
+ * does not know is refused, so the struct can grow.  opts NULL: scale_mode 0. */
+typedef struct {
+  int32_t struct_size; /* sizeof(ptzba_cov_opts) */
+  int32_t scale_mode;  /* 0: scale = 1 (plain H^-1); 1: the given `scale`; 2: the residual variance estimate
+                          s^2 = sum(rho' r^2) / (2 R - n_free) over the R records */
+  double scale;
+} ptzba_cov_opts;
+PTZBA_EXPORT int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* opts, double* pose_cov,
+                                  const int32_t* lm_index, int32_t n_lm, double* ray_cov, double* info);
 /* Which front builds the record arrays in the following ptzba_set_problem calls of this handle (round 6): the device
  * front (one rocPRIM radix sort + segment / record kernels) from min_records records on, the host's counting sorts
  * below.  0: always the device, INT64_MAX: never, -1: the default (64K records since round 6, 4M before: configs 3 and 4

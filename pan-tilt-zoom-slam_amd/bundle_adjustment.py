@@ -124,8 +124,12 @@ class _KeyframeLists:
 
 def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, center, rotation, u, v, save_path,
                       verbose=False, precision="fp64", loss="linear", f_scale=1.0, ftol=1e-4, xtol=1e-8,
-                      max_iter=100, device=0, correspondences=None):
+                      max_iter=100, device=0, correspondences=None, *, covariance=False):
     """bundle_adjustment.py:109-251 on the MI355X path.  Returns (landmarks [M,2], keyframes).
+    covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
+    `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
+    (row l belongs to landmarks[l]) and `info`: the posterior covariance blocks (J^T J)^-1 at the returned solution
+    (ptzba.BAHandle.covariance; with loss='huber' the IRLS-weighted normal matrix).
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
@@ -184,12 +188,16 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     all_poses = initial_ptzs.copy()
     landmarks = rays0.copy()
     res = None
+    cov = dict(pose_cov=np.zeros((N, 3, 3)), ray_cov=np.zeros((n_landmark, 2, 2)), info={})  # (no records: no blocks)
     if len(frame):
         prec = ptzba.FP32 if precision == "fp32" else ptzba.FP64
         ls = ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR
-        all_poses, landmarks, res = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec,
-                                                loss=ls, f_scale=f_scale, device=device, ftol=ftol, xtol=xtol,
-                                                max_iter=max_iter)
+        out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
+                          f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
+                          covariance=True if covariance else None)
+        all_poses, landmarks, res = out[:3]
+        if covariance:
+            cov = dict(pose_cov=out[3][0], ray_cov=out[3][1], info=out[3][2])
         all_poses[0] = ref_pose
         if verbose:
             print(f"GPU LM: {res}")
@@ -214,4 +222,6 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     LAST_RESULT.clear()
     LAST_RESULT.update(result=res, n_residual=n_residual, n_landmark=n_landmark, time=timing["solve"],
                        timing=timing, x0=np.concatenate([initial_ptzs[1:].reshape(-1), rays0.reshape(-1)]))
+    if covariance:
+        return landmarks, keyframes, cov
     return landmarks, keyframes

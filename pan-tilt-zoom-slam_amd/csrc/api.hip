@@ -120,6 +120,14 @@ struct ptzba_ctx {
   DBuf ztiles;  // tiles zeroed before each build (the rest of the system region stays zero)
   int n_ztiles = 0;
   double lambda = 0;
+  // posterior covariance (ptzba_covariance): its plan and buffers, built by the first call after a set_problem
+  struct Cov {
+    bool ready = false;
+    int n_tiles = 0, n_pose_blocks = 0, n_active = 0, max_groups = 256;
+    DBuf row_off, row_col, row_frame, pose_rows, pose_frame, pose_t0;  // cov_kernels.hip CovArgs
+    DBuf Minv, min_piv, work, D_saved, pose_out, ray_out, lm_index, resid;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } cov;
   // device-driven LM: state, pinned record ring, events
   DBuf lmdev;
   LMDev* lm_host = nullptr;
@@ -256,7 +264,8 @@ static hipEvent_t tm_k1_event(ptzba_ctx* h, int which) {
 const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.2 (round 6): ptzba_lm_opts carries huber_curvature / curvature_switch (11 fields; 0.1 had 9).  They are read
 // for the Huber loss only, and huber_curvature 0 means the default 0.1, so a zero-filled tail keeps 0.1's behaviour.
-const char* ptzba_version(void) { return "ptzba 0.2 gfx950 (ptzba_lm_opts: 11 fields)"; }
+// 0.3: ptzba_covariance / ptzba_cov_opts (sized by its struct_size field); ptzba_lm_opts as in 0.2.
+const char* ptzba_version(void) { return "ptzba 0.3 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance)"; }
 
 ptzba_handle ptzba_new(int device) {
   if (select_device(device)) return nullptr;
@@ -278,6 +287,8 @@ void ptzba_delete(ptzba_handle h) {
   for (int k = 0; k < TM_N; ++k)
     for (auto e : h->ev[k]) (void)hipEventDestroy(e);
   for (auto e : h->cev) (void)hipEventDestroy(e);
+  for (auto e : h->cov.ev)
+    if (e) (void)hipEventDestroy(e);
   if (h->own) (void)hipStreamDestroy(h->own);
   if (h->scal_host) (void)hipHostFree(h->scal_host);
   if (h->out_pin) (void)hipHostFree(h->out_pin);
@@ -2040,6 +2051,7 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   if (!h->scal_pack.p && h->scal_pack.alloc(24 * sizeof(double))) return -1;
   h->cur = 0;
   h->lambda = 0;
+  h->cov.ready = false;  // (the covariance plan of the previous problem)
   HIPCHK(hipStreamSynchronize(h->st));  // every initialisation above has landed before the handle is used
   st_mark("final sync");
   h->have_problem = true;
@@ -2404,12 +2416,9 @@ int ptzba_build_reduced(ptzba_handle h, double lambda) {
   return build_impl(h, lambda, nullptr);
 }
 
-// damped solve, trial state, trial linearisation into slot `nx` and the trial scalars (device-driven LM:
-// current slot *sel, trial slot *sel ^ 1, chosen on the device)
-static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* sel = nullptr) {
-  const int c = sel ? 0 : h->cur;
-  if (sel) nx = 1;  // the trial's slot, with the other slot as the selector's alternative
-  tm_begin(h, TM_CHOL);
+// prepare (augmented row, padding, pose damping with h->lambda or *lam_dev) and factor the built reduced system: the
+// front of a solve, and of ptzba_covariance at lambda = 0
+static int factor_impl(ptzba_ctx* h, const double* lam_dev, const int* sel) {
   const int4* th = reinterpret_cast<const int4*>(h->chol_tasks_host.data());
   if (h->dist_mode) {
     // the rank's phases (make_plan_tree): before each later phase its columns are summed over its node's group
@@ -2437,6 +2446,16 @@ static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* se
                       h->Ldiag.as<double>(), h->info.as<int>(), h->st, nullptr, th, h->Minv.as<double>(), 0,
                       h->chol_delayed);
   }
+  return 0;
+}
+
+// damped solve, trial state, trial linearisation into slot `nx` and the trial scalars (device-driven LM:
+// current slot *sel, trial slot *sel ^ 1, chosen on the device)
+static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* sel = nullptr) {
+  const int c = sel ? 0 : h->cur;
+  if (sel) nx = 1;  // the trial's slot, with the other slot as the selector's alternative
+  tm_begin(h, TM_CHOL);
+  if (factor_impl(h, lam_dev, sel)) return -1;
   if (h->bs_pst)
     launch_chol_backsolve_pst(h->S(), h->ld, h->n_aug, h->bsb_tasks.as<int4>(), h->bsp_expect.as<int4>(),
                               h->bsb_step_off.back(), h->Ldiag.as<double>(), h->Minv.as<double>(), h->bsb_r.as<double>(),
@@ -3466,6 +3485,219 @@ int ptzba_set_huber_curvature(ptzba_handle h, double hc) {
   if (!h) return fail("null handle");
   if (!(hc > 0.0 && hc <= 1.0)) return fail("huber curvature must lie in (0, 1]");
   h->hcurv = hc;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// posterior covariance: diagonal blocks of scale * H^-1 at the current state (cov_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// the covariance plan of the current problem, from the device copies of the solver's own structure (a solve keeps no
+// host copy of them): row CSR of the factor's tile pattern, row -> frame map, pose column blocks in system order
+constexpr int COV_WG_PER_CU = 2;
+constexpr size_t COV_WORK_BYTES = (size_t)192 << 20;  // cap of the Z workspace (MI355X Infinity Cache: 256 MB)
+static int cov_prepare(ptzba_ctx* h) {
+  auto& c = h->cov;
+  if (c.ready) return 0;
+  std::vector<int32_t> zt(2 * (size_t)h->n_ztiles), pos(h->n_pose), seg(h->n_lm + 1);
+  HIPCHK(hipMemcpyAsync(zt.data(), h->ztiles.p, zt.size() * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(pos.data(), h->frame_pos.p, pos.size() * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(seg.data(), h->lm_seg_begin.p, seg.size() * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  const int T = (h->n_aug + CHOL_NB - 1) / CHOL_NB;
+  std::vector<std::vector<int>> rows(T);
+  for (int q = 0; q < h->n_ztiles; ++q) {
+    const int i = zt[2 * q], j = zt[2 * q + 1];
+    if (j < i && i < T) rows[i].push_back(j);
+  }
+  std::vector<int> off(T + 1, 0), col;
+  for (int i = 0; i < T; ++i) {
+    std::sort(rows[i].begin(), rows[i].end());
+    col.insert(col.end(), rows[i].begin(), rows[i].end());
+    off[i + 1] = (int)col.size();
+  }
+  if (col.empty()) col.push_back(0);
+  std::vector<int32_t> row_frame(std::max(h->n_aug, 1), -1);
+  std::vector<std::pair<int, int>> free_frames;  // (system row, frame)
+  for (int f = 0; f < h->n_pose; ++f) {
+    if (pos[f] < 0) continue;
+    if (pos[f] + 2 >= h->n_aug) return fail("covariance plan: frame %d lies outside the system", f);
+    for (int q = 0; q < 3; ++q) row_frame[pos[f] + q] = f;
+    free_frames.emplace_back(pos[f], f);
+  }
+  std::sort(free_frames.begin(), free_frames.end());
+  const int nb = ((int)free_frames.size() + COV_POSE_F - 1) / COV_POSE_F;
+  std::vector<int32_t> prow((size_t)std::max(nb, 1) * CHOL_NB, -1), pfr((size_t)std::max(nb, 1) * COV_POSE_F, -1),
+      pt0(std::max(nb, 1), 0);
+  for (int k = 0; k < (int)free_frames.size(); ++k) {
+    const int b = k / COV_POSE_F, q = k % COV_POSE_F;
+    for (int x = 0; x < 3; ++x) prow[(size_t)b * CHOL_NB + 3 * q + x] = free_frames[k].first + x;
+    pfr[(size_t)b * COV_POSE_F + q] = free_frames[k].second;
+    if (q == 0) pt0[b] = free_frames[k].first / CHOL_NB;
+  }
+  c.n_active = 0;
+  for (int l = 0; l < h->n_lm; ++l) c.n_active += seg[l + 1] > seg[l];
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, h->device));
+  // workgroups in flight: COV_WG_PER_CU per CU (one wave per SIMD each; 18 KB of LDS and ~100 VGPRs would let four be
+  // resident), as long as their Z workspaces together stay inside the Infinity Cache (knob: PTZBA_COV_WG_PER_CU)
+  const char* gpc = getenv("PTZBA_COV_WG_PER_CU");
+  const int per_cu = gpc ? std::min(std::max(atoi(gpc), 1), 8) : COV_WG_PER_CU;
+  const size_t per_block = (size_t)std::max(T, 1) * CHOL_NB * CHOL_NB * 8;
+  c.max_groups = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(prop.multiProcessorCount, 1) * per_cu,
+                                                           COV_WORK_BYTES / per_block));
+  if (upload(c.row_off, off, h->st) || upload(c.row_col, col, h->st) || upload(c.row_frame, row_frame, h->st) ||
+      upload(c.pose_rows, prow, h->st) || upload(c.pose_frame, pfr, h->st) || upload(c.pose_t0, pt0, h->st) ||
+      c.Minv.alloc((size_t)std::max(T, 1) * CHOL_NB * CHOL_NB * 8) || c.min_piv.alloc((size_t)std::max(T, 1) * 8) ||
+      c.D_saved.alloc(h->D_pose.bytes + h->D_ray.bytes) || c.resid.alloc((1024 + 8) * 8))
+    return -1;
+  for (auto& e : c.ev)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  c.n_tiles = T;
+  c.n_pose_blocks = nb;
+  c.ready = true;
+  return 0;
+}
+
+// Between solves (no trial pending): linearises the current state with IRLS curvature, builds and factors the
+// undamped reduced system and runs the selected inverse, all on the handle's stream; leaves the handle as
+// ptzba_linearize does, with the Marquardt scales, the damping and the huber curvature setting of the caller's run
+// restored, so a solve started afterwards takes bitwise the steps it takes without the call.
+int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* o, double* pose_cov, const int32_t* lm_index, int32_t n_lm,
+                     double* ray_cov, double* info) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  ptzba_cov_opts opt{(int32_t)sizeof(ptzba_cov_opts), 0, 1.0};
+  if (o) {
+    if (o->struct_size != (int32_t)sizeof(ptzba_cov_opts))
+      return fail("ptzba_covariance: unknown struct_size %d of ptzba_cov_opts (this library knows %d)",
+                  (int)o->struct_size, (int)sizeof(ptzba_cov_opts));
+    opt = *o;
+  }
+  if (opt.scale_mode < 0 || opt.scale_mode > 2) return fail("ptzba_covariance: bad options (scale_mode %d)", opt.scale_mode);
+  if (opt.scale_mode == 1 && !(opt.scale > 0.0 && std::isfinite(opt.scale)))
+    return fail("ptzba_covariance: bad options (scale must be positive and finite)");
+  if (h->dist_mode || h->dist_world > 1 || h->has_exchange() || h->ext_exchange)
+    return fail("ptzba_covariance is single-rank only (the handle is sharded or has a communicator / hook attached)");
+  if (n_lm < -1) return fail("ptzba_covariance: bad landmark count %d", n_lm);
+  const int64_t n_sel = n_lm < 0 ? h->n_lm : n_lm;
+  if (n_lm > 0 && !lm_index) return fail("ptzba_covariance: null landmark index list");
+  if (n_sel > 0 && !ray_cov) return fail("ptzba_covariance: null ray covariance buffer");
+  for (int32_t k = 0; k < n_lm; ++k)
+    if (lm_index[k] < 0 || lm_index[k] >= h->n_lm)
+      return fail("ptzba_covariance: landmark index %d out of range [0, %d)", lm_index[k], h->n_lm);
+  HIPCHK(hipSetDevice(h->device));
+  if (cov_prepare(h)) return -1;
+  auto& c = h->cov;
+  const int n_free = 3 * (h->n_pose - h->n_fixed) + 2 * c.n_active;
+  const double dof = 2.0 * (double)h->n_rec - (double)n_free;
+  if (opt.scale_mode == 2 && !(dof > 0)) return fail("ptzba_covariance: residual scale needs more residuals (%lld) than "
+                                                     "free parameters (%d)", (long long)(2 * h->n_rec), n_free);
+  const int n_ray_blocks = (int)((n_sel + CHOL_NB / 2 - 1) / (CHOL_NB / 2));
+  const int n_pose_blocks = pose_cov ? c.n_pose_blocks : 0;
+  const int n_groups = std::min(c.max_groups, n_pose_blocks + n_ray_blocks);
+  if (c.work.reserve((size_t)std::max(n_groups, 1) * std::max(c.n_tiles, 1) * CHOL_NB * CHOL_NB * 8) ||
+      c.pose_out.reserve((size_t)h->n_pose * 9 * 8) || c.ray_out.reserve((size_t)std::max<int64_t>(n_sel, 1) * 4 * 8) ||
+      c.lm_index.reserve((size_t)std::max<int32_t>(n_lm, 1) * 4))
+    return -1;
+  SyncOnExit sync_guard{h->st};  // caller buffers and the stack below outlive every queued copy, also on errors
+  // the caller's run state this call borrows: huber curvature, damping, timing groups
+  struct Restore {
+    ptzba_ctx* h;
+    double hcurv, lambda;
+    int timing;
+    ~Restore() { h->hcurv = hcurv; h->lambda = lambda; h->timing = timing; }
+  } restore{h, h->hcurv, h->lambda, h->timing};
+  h->hcurv = 1.0;
+  h->lambda = 0.0;
+  h->timing = 0;
+  if (n_lm > 0) HIPCHK(hipMemcpyAsync(c.lm_index.p, lm_index, (size_t)n_lm * 4, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipEventRecord(c.ev[0], h->st));
+  // the Marquardt scales are a monotone memory of the run: a build raises them, so they are put back afterwards
+  double* dsave = c.D_saved.as<double>();
+  HIPCHK(hipMemcpyAsync(dsave, h->D_pose.p, h->D_pose.bytes, hipMemcpyDeviceToDevice, h->st));
+  HIPCHK(hipMemcpyAsync(dsave + h->D_pose.bytes / 8, h->D_ray.p, h->D_ray.bytes, hipMemcpyDeviceToDevice, h->st));
+  if (ptzba_linearize(h)) return -1;
+  double* resid = c.resid.as<double>();  // [0] the weighted residual sum | [8, ...) partials
+  if (opt.scale_mode == 2) {
+    const int n_part = (int)std::min<int64_t>(1024, (h->n_rec + 255) / 256);
+    if (h->precision == PTZBA_FP32)
+      launch_cov_resid<float>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
+                              h->seg_base.as<double2>(), h->rec_xy.p, h->weighted ? h->rec_w.p : nullptr, h->ft64.p,
+                              h->rt64.p, h->u, h->v, h->n_rec, h->loss == PTZBA_LOSS_HUBER, h->fs, resid + 8, n_part,
+                              resid, h->st);
+    else
+      launch_cov_resid<double>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
+                               h->seg_base.as<double2>(), h->rec_xy.p, h->weighted ? h->rec_w.p : nullptr, h->ft64.p,
+                               h->rt64.p, h->u, h->v, h->n_rec, h->loss == PTZBA_LOSS_HUBER, h->fs, resid + 8, n_part,
+                               resid, h->st);
+  }
+  if (build_impl(h, 0.0, nullptr) || factor_impl(h, nullptr, nullptr)) return -1;
+  HIPCHK(hipMemcpyAsync(h->D_pose.p, dsave, h->D_pose.bytes, hipMemcpyDeviceToDevice, h->st));
+  HIPCHK(hipMemcpyAsync(h->D_ray.p, dsave + h->D_pose.bytes / 8, h->D_ray.bytes, hipMemcpyDeviceToDevice, h->st));
+  launch_cov_tile_inv(h->Ldiag.as<double>(), h->row_pad.as<uint8_t>(), h->n_aug, c.n_tiles, c.Minv.as<double>(),
+                      c.min_piv.as<double>(), h->st);
+  if (pose_cov) HIPCHK(hipMemsetAsync(c.pose_out.p, 0, (size_t)h->n_pose * 9 * 8, h->st));
+  CovArgs a;
+  a.L = h->S();
+  a.ld = h->ld;
+  a.n_aug = h->n_aug;
+  a.n_tiles = c.n_tiles;
+  a.Minv = c.Minv.as<double>();
+  a.row_off = c.row_off.as<int>();
+  a.row_col = c.row_col.as<int>();
+  a.frame_pos = h->frame_pos.as<int32_t>();
+  a.row_frame = c.row_frame.as<int32_t>();
+  a.work = c.work.as<double>();
+  a.scale = opt.scale_mode == 1 ? opt.scale : 1.0;
+  a.scale_dev = opt.scale_mode == 2 ? resid : nullptr;
+  a.scale_div = dof;
+  a.n_pose_blocks = n_pose_blocks;
+  a.pose_rows = c.pose_rows.as<int32_t>();
+  a.pose_frame = c.pose_frame.as<int32_t>();
+  a.pose_t0 = c.pose_t0.as<int32_t>();
+  a.pose_cov = c.pose_out.as<double>();
+  a.n_ray_blocks = n_ray_blocks;
+  a.n_lm_sel = n_sel;
+  a.lm_index = n_lm < 0 ? nullptr : c.lm_index.as<int32_t>();
+  a.w_slot = h->w_slot[h->cur].p;
+  a.lm_aux = h->lm_aux.as<double>();
+  a.lm_meta = h->lm_meta.as<int4>();
+  a.lm_seg_begin = h->lm_seg_begin.as<int32_t>();
+  a.ray_cov = c.ray_out.as<double>();
+  if (h->precision == PTZBA_FP32) launch_cov_gram<float>(a, n_groups, h->st);
+  else launch_cov_gram<double>(a, n_groups, h->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(c.ev[1], h->st));
+  // the factor's verdict first: nothing is copied out of a failed factorisation
+  std::vector<double> piv(std::max(c.n_tiles, 1), 1.0);
+  int finfo = 0;
+  double rsum = 0.0;
+  HIPCHK(hipMemcpyAsync(piv.data(), c.min_piv.p, (size_t)c.n_tiles * 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipMemcpyAsync(&finfo, h->info.p, sizeof(int), hipMemcpyDeviceToHost, h->st));
+  if (opt.scale_mode == 2) HIPCHK(hipMemcpyAsync(&rsum, resid, 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  double min_pivot = 1e300;
+  bool bad = false;
+  for (int t = 0; t < c.n_tiles; ++t) {
+    if (!(piv[t] > 0.0) || !std::isfinite(piv[t])) bad = true;
+    if (piv[t] < min_pivot) min_pivot = piv[t];
+  }
+  if (finfo != 0 || bad)
+    return fail("ptzba_covariance: the undamped reduced system is not positive definite (factorisation info %d, "
+                "non-positive pivot: %s) -- a free frame without observations makes it singular", finfo,
+                bad ? "yes" : "no");
+  const double scale = opt.scale_mode == 2 ? rsum / dof : a.scale;
+  if (!(scale > 0.0) || !std::isfinite(scale)) return fail("ptzba_covariance: the residual scale is not positive (%g)", scale);
+  if (pose_cov) HIPCHK(hipMemcpyAsync(pose_cov, c.pose_out.p, (size_t)h->n_pose * 9 * 8, hipMemcpyDeviceToHost, h->st));
+  if (n_sel > 0) HIPCHK(hipMemcpyAsync(ray_cov, c.ray_out.p, (size_t)n_sel * 4 * 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  if (info) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    info[0] = scale;
+    info[1] = min_pivot;
+    info[2] = (double)n_free;
+    info[3] = (double)ms;
+  }
   return 0;
 }
 

@@ -316,6 +316,48 @@ inline int chol_pack_type(int type, int p3, int p4, int tmask34) {
   return (int)((unsigned)type | ((unsigned)(p3 + 1) << 2) | ((unsigned)(p4 + 1) << 16) | ((unsigned)tmask34 << 30));
 }
 
+// posterior covariance blocks (cov_kernels.hip): one workgroup per 32-column right-hand-side block -- a pose block is
+// COV_POSE_F frames x 3 unit columns, a ray block CHOL_NB / 2 landmarks x 2 columns of W V^-1 -- forward-substituted
+// through the factor's row tiles; the 3 x 3 / 2 x 2 diagonal blocks of scale * (Z^T Z (+ V^-1)) are written
+constexpr int COV_POSE_F = 10;
+struct CovArgs {
+  const double* L;             // [ld][ld] the factored system (off-diagonal tiles of L)
+  int64_t ld;
+  int n_aug, n_tiles;          // system rows before the augmented row; row tiles holding them
+  const double* Minv;          // [n_tiles][32][32] masked diagonal-tile inverses (launch_cov_tile_inv)
+  const int* row_off;          // [n_tiles + 1] row CSR of the factor's pattern, strictly lower tiles, ascending
+  const int* row_col;
+  const int32_t* frame_pos;    // [n_pose] system row of the frame's pan (-1: fixed)
+  const int32_t* row_frame;    // [n_aug] frame of a system row (-1: padding)
+  double* work;                // [workgroups][n_tiles][32][32] the Z tiles of the block a workgroup is on
+  double scale;                // the blocks' factor, or with scale_dev != nullptr: scale_dev[0] / scale_div
+  const double* scale_dev;
+  double scale_div;
+  int n_pose_blocks;
+  const int32_t* pose_rows;    // [n_pose_blocks][32] system row of each unit column (-1: none)
+  const int32_t* pose_frame;   // [n_pose_blocks][COV_POSE_F] frame of each column triple (-1: none)
+  const int32_t* pose_t0;      // [n_pose_blocks] first non-zero tile
+  double* pose_cov;            // [n_pose][3][3]
+  int n_ray_blocks;
+  int64_t n_lm_sel;            // selected landmarks
+  const int32_t* lm_index;     // [n_lm_sel], or nullptr: landmark q is the q-th
+  const void* w_slot;          // current linearisation: W (real) by dense slot
+  const double* lm_aux;        // [n_lm][8] V^-1 (3) | ...
+  const int4* lm_meta;         // [n_lm] {first frame, last frame, slot offset, 0}
+  const int32_t* lm_seg_begin; // [n_lm + 1]
+  double* ray_cov;             // [n_lm_sel][2][2]
+};
+// min_piv [n_tiles]: the smallest pivot of each tile's system rows (NaN: not a number)
+void launch_cov_tile_inv(const double* Ldiag, const uint8_t* pad, int n_aug, int n_tiles, double* Minv,
+                         double* min_piv, hipStream_t st);
+template <typename real>
+void launch_cov_gram(const CovArgs& a, int n_groups, hipStream_t st);
+// out[0] = sum over the scalar residuals of w rho' r^2 at the current tables (part: n_part doubles of scratch)
+template <typename real>
+void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
+                      const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
+                      int64_t n_rec, int huber, double f_scale, double* part, int n_part, double* out, hipStream_t st);
+
 // camera batch kernels (camera_kernels.hip)
 void launch_ray_to_image(int64_t n, double u, double v, const double* f, const double* cp, const double* ct,
                          const double* th, const double* ph, double* x, double* y, hipStream_t st);

@@ -69,6 +69,14 @@ class ptzba_lm_record(Structure):
                 ("accepted", c_int32)]
 
 
+class ptzba_cov_opts(Structure):
+    """include/ptzba.h ptzba_cov_opts; struct_size = ctypes.sizeof(ptzba_cov_opts) (the library refuses another)."""
+    _fields_ = [("struct_size", c_int32), ("scale_mode", c_int32), ("scale", c_double)]
+
+
+COV_SCALE_UNIT, COV_SCALE_GIVEN, COV_SCALE_RESIDUAL = 0, 1, 2
+
+
 class ptzba_report(Structure):
     _fields_ = [("cost", c_double), ("initial_cost", c_double), ("time_s", c_double), ("iterations", c_int32),
                 ("nfev", c_int32), ("trials", c_int32), ("status", c_int32)]
@@ -125,6 +133,7 @@ def lib():
         "ptzba_solve_reduced": ([V], I),
         "ptzba_step": ([V, D], I),
         "ptzba_set_huber_curvature": ([V, D], I),
+        "ptzba_covariance": ([V, POINTER(ptzba_cov_opts), V, V, I32, V, V], I),
         "ptzba_set_setup_front": ([V, I64], I),
         "ptzba_setup_timing": ([V, I32, V, V, V], I),
         "ptzba_solve": ([V, V, V, POINTER(ptzba_lm_opts), POINTER(ptzba_report)], I),
@@ -230,7 +239,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_dist_info", "ptzba_owned_frames", "ptz_corner_min_eig", "ptz_orb", "ptzba_plan_summary",
     "ptzba_plan_export", "ptzba_dist_exchanges", "ptzba_dist_groups", "ptzba_exchange_group", "ptzba_dist_plan_summary",
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
-    "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac",
+    "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
 ]
 
 
@@ -1133,6 +1142,40 @@ class BAHandle:
         """Host-driven LM: the huber curvature weight (units of rho' beyond the unit) of later linearisations."""
         _check(lib().ptzba_set_huber_curvature(self.h, float(hc)), "ptzba_set_huber_curvature")
 
+    def covariance(self, landmarks=None, scale=None, poses=True, _struct_size=None):
+        """Posterior covariance blocks at the current state (ptzba_covariance; a between-solves call): the diagonal
+        blocks of scale * (J^T diag(rho') J)^-1 over the free parameters.  landmarks: None (no rays), "all", or an
+        int array of landmark indices (duplicates allowed); scale: None (1), a positive float, or "residual"
+        (s^2 = sum(rho' r^2) / (2 R - n_free)); poses=False skips the pose blocks.  Returns (pose_cov [n_pose, 3, 3]
+        with the fixed frames' blocks zero, or None; ray_cov [k, 2, 2] or None; info dict: scale, min_pivot, n_free,
+        device_ms).  Raises PtzbaError when the undamped system is not positive definite."""
+        if scale is None:
+            mode, sval = COV_SCALE_UNIT, 1.0
+        elif isinstance(scale, str):
+            if scale != "residual":
+                raise ValueError("scale must be None, a positive number or 'residual'")
+            mode, sval = COV_SCALE_RESIDUAL, 1.0
+        else:
+            mode, sval = COV_SCALE_GIVEN, float(scale)
+        opts = ptzba_cov_opts(ctypes.sizeof(ptzba_cov_opts) if _struct_size is None else int(_struct_size), mode, sval)
+        pose_cov = np.zeros((self.n_pose, 3, 3)) if poses else None
+        idx = None
+        if landmarks is None:
+            n_lm, ray_cov = 0, None
+        elif isinstance(landmarks, str):
+            if landmarks != "all":
+                raise ValueError("landmarks must be None, 'all' or an index array")
+            n_lm, ray_cov = -1, np.zeros((self.n_landmark, 2, 2))
+        else:
+            idx = np.ascontiguousarray(landmarks, dtype=np.int32).reshape(-1)
+            n_lm, ray_cov = len(idx), np.zeros((len(idx), 2, 2))
+        info = np.zeros(4)
+        _check(lib().ptzba_covariance(self.h, ctypes.byref(opts), _ptr(pose_cov), _ptr(idx), n_lm,
+                                      _ptr(ray_cov) if ray_cov is not None and ray_cov.size else c_void_p(0),
+                                      _ptr(info)), "ptzba_covariance")
+        return pose_cov, ray_cov, dict(scale=float(info[0]), min_pivot=float(info[1]), n_free=int(info[2]),
+                                       device_ms=float(info[3]))
+
     def build_reduced(self, lam):
         _check(lib().ptzba_build_reduced(self.h, float(lam)), "ptzba_build_reduced")
 
@@ -1384,6 +1427,10 @@ class LMSolver:
             self.allreduce("scal")
         return self.h.read_scalars()
 
+    def covariance(self, landmarks=None, scale=None, poses=True):
+        """BAHandle.covariance at the solver's solution (the handle's current state; call it after run())."""
+        return self.h.covariance(landmarks=landmarks, scale=scale, poses=poses)
+
     def run(self, iterations=None, check_termination=True):
         if self.device_loop and check_termination and not self.verbose:
             return self._run_device(iterations)
@@ -1573,9 +1620,15 @@ def warm_up(device=0, precision=FP64):
 SETUP_FRONT_MIN = None
 
 
+def _cov_kwargs(covariance):
+    return dict(covariance) if isinstance(covariance, dict) else dict(landmarks="all")
+
+
 def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, weight=None, precision=FP64,
-          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, **lm_kw):
-    """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult).  keep_handle=True (default): one
+          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, **lm_kw):
+    """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
+    BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
+    (pose_cov, ray_cov, info) at the solution.  keep_handle=True (default): one
     handle per device is kept between calls (a keyframe map solves on every new keyframe: creating and
     destroying a handle -- stream, pinned records, device buffers -- cost ~6 ms per call); set_problem replaces
     its problem and release_solve_handles() frees it.  keep_handle=False: a private handle, closed on return.
@@ -1588,6 +1641,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
             h.set_state(init_ptz, init_rays)
             res = LMSolver(h, **lm_kw).run()
             ptz, rays = h.get_state()
+            if covariance:
+                return ptz, rays, res, h.covariance(**_cov_kwargs(covariance))
             return ptz, rays, res
         finally:
             h.close()
@@ -1612,6 +1667,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                 LAST_SOLVE_TIMING["setup_" + k.replace("+", "_").replace(" ", "_") + "_s"] = v * 1e-3
             LAST_SOLVE_TIMING.update(set_problem_s=t1 - t0, lm_s=time.perf_counter() - t1, lm_set_state_s=t2 - t1,
                                      lm_run_s=t3 - t2, lm_get_state_s=time.perf_counter() - t3)
+            if covariance:
+                return ptz, rays, res, h.covariance(**_cov_kwargs(covariance))
             return ptz, rays, res
         except Exception:
             _solve_handles.pop(device, None)
