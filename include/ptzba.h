@@ -285,6 +285,43 @@ typedef struct {
 } ptzba_cov_opts;
 PTZBA_EXPORT int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* opts, double* pose_cov,
                                   const int32_t* lm_index, int32_t n_lm, double* ray_cov, double* info);
+/* Gaussian pose priors (ptzba_version 0.4).  A prior is a list of factors; factor k names G_k distinct free frames
+ * (1 <= G_k <= 8), a mean mu_k of 3 G_k values and a symmetric positive semi-definite information matrix Lambda_k of
+ * size 3 G_k x 3 G_k, per frame in the order pan, tilt, f.  The objective becomes
+ *     cost = 1/2 sum rho(r^2) + 1/2 sum_k e_k^T Lambda_k e_k,     e_k = x_{F_k} - mu_k
+ * (the loss never applies to the prior terms).  The pose gradient gains Lambda_k e_k and the Gauss-Newton matrix the
+ * constant P = sum_k Lambda_k on its pose blocks, so every solve path, the Marquardt scaling (diag P counts as the
+ * whitened prior rows' column norms would), every reported cost (ptzba_read_scalars [0] / [1], ptzba_lm_record,
+ * ptzba_report), the gradient maximum and ptzba_covariance (blocks of scale * (J^T J + P)^-1) include the prior.
+ * ptzba_covariance's scale_mode 2 becomes s^2 = (sum rho' r^2 + sum_k e_k^T Lambda_k e_k) / (2 R + sum_k 3 G_k -
+ * n_free): every prior row counts as one residual, which over-counts the rows of a rank-deficient Lambda_k.
+ *
+ * Layout: factor k's frames are frames[factor_begin[k] .. factor_begin[k + 1]) (factor_begin[0] = 0), its mean the
+ * 3 values per listed frame at mean[3 factor_begin[k] ..], its information matrix the next (3 G_k)^2 row-major values
+ * of info (the blocks concatenated in factor order).  The arrays are copied.  NULL or n_factor == 0 clears the priors.
+ * Valid after ptzba_set_problem, between solves (no LM trial pending; the next ptzba_linearize / ptzba_lm_start picks
+ * the new cost up).  ptzba_set_problem clears the priors; they persist over ptzba_set_state / ptzba_save_state /
+ * ptzba_restore_state.
+ * Refused with a message, the handle left as it was: a struct_size this library does not know; a frame < n_fixed or
+ * >= n_pose; a frame repeated inside one factor; G outside 1..8; a non-finite value; a negative diagonal entry of
+ * Lambda; asymmetry beyond 1e-12 max|Lambda_k| (anything within that bound is symmetrised); a pair f < f' of one
+ * factor with f' beyond the handle's coupling window of f (the factor pattern has no tile for it: raise
+ * ptzba_problem_opts.frame_win_hi[f] to f' at ptzba_set_problem); a sharded handle, or one with a communicator or
+ * hook attached or a caller-run exchange protocol in use.  While priors are set, ptzba_attach_comm and
+ * ptzba_set_exchange_hook are refused.  Lambda's definiteness beyond its diagonal is the caller's to ensure (ptzba.py
+ * checks the eigenvalues). */
+typedef struct {
+  int32_t struct_size;          /* sizeof(ptzba_pose_priors) */
+  int32_t n_factor;
+  const int32_t* factor_begin;  /* [n_factor + 1] */
+  const int32_t* frames;        /* [factor_begin[n_factor]] */
+  const double* mean;           /* [3 factor_begin[n_factor]] */
+  const double* info;           /* [sum_k (3 G_k)^2] */
+} ptzba_pose_priors;
+PTZBA_EXPORT int ptzba_set_pose_priors(ptzba_handle h, const ptzba_pose_priors* priors);
+/* out4: [0] factors, [1] prior rows sum_k 3 G_k, [2] distinct 3 x 3 blocks of P (unordered frame pairs, the diagonal
+ * ones included), [3] the prior cost 1/2 sum_k e_k^T Lambda_k e_k at the handle's current state (0 without priors) */
+PTZBA_EXPORT int ptzba_pose_prior_info(ptzba_handle h, double* out4);
 /* Which front builds the record arrays in the following ptzba_set_problem calls of this handle (round 6): the device
  * front (one rocPRIM radix sort + segment / record kernels) from min_records records on, the host's counting sorts
  * below.  0: always the device, INT64_MAX: never, -1: the default (64K records since round 6, 4M before: configs 3 and 4

@@ -124,12 +124,16 @@ class _KeyframeLists:
 
 def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, center, rotation, u, v, save_path,
                       verbose=False, precision="fp64", loss="linear", f_scale=1.0, ftol=1e-4, xtol=1e-8,
-                      max_iter=100, device=0, correspondences=None, *, covariance=False):
+                      max_iter=100, device=0, correspondences=None, *, covariance=False, pose_priors=None):
     """bundle_adjustment.py:109-251 on the MI355X path.  Returns (landmarks [M,2], keyframes).
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
     (row l belongs to landmarks[l]) and `info`: the posterior covariance blocks (J^T J)^-1 at the returned solution
     (ptzba.BAHandle.covariance; with loss='huber' the IRLS-weighted normal matrix).
+    pose_priors (keyword only; off: the call and its outputs are unchanged): Gaussian pose prior factors
+    [(image indices, mean, info), ...] keyed by image index (entries of image_indices) -- ptzba.check_pose_priors'
+    factor form, 1/2 e^T info e with e = the named images' (pan, tilt, f) minus mean, added to the objective.  A factor
+    on the call's first image (the gauge, held fixed) or on an image that is not part of the call raises ValueError.
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
@@ -140,6 +144,18 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     assert initial_ptzs.shape[0] == N and initial_ptzs.shape[1] == 3
     assert np.asarray(center).shape[0] == 3 and np.asarray(rotation).shape == (3, 3)
     assert feature_method in ("sift", "orb", "latch")
+    priors = None
+    if pose_priors:
+        where = {k: i for i, k in enumerate(image_indices)}
+        priors = []
+        for n, (keys, mean, info) in enumerate(pose_priors):
+            keys = np.atleast_1d(np.asarray(keys)).tolist()
+            if any(k not in where for k in keys):
+                raise ValueError(f"pose prior {n}: image index not among image_indices")
+            if any(where[k] == 0 for k in keys):
+                raise ValueError(f"pose prior {n}: image {image_indices[0]} is the gauge frame (held fixed)")
+            priors.append(([where[k] for k in keys], mean, info))
+        priors = ptzba.check_pose_priors(priors, N)
     timing = {}
     t_start = time.time()
 
@@ -194,7 +210,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         ls = ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
-                          covariance=True if covariance else None)
+                          covariance=True if covariance else None, pose_priors=priors)
         all_poses, landmarks, res = out[:3]
         if covariance:
             cov = dict(pose_cov=out[3][0], ray_cov=out[3][1], info=out[3][2])

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -192,7 +193,19 @@ struct ptzba_ctx {
   bool f1_covered = false;     // every 32-frame block has a chunk-0 Schur tile (all diagonals written by K2)
   // single-GPU builds fold k_chol_prepare into the build (FusedPrep, ptzba_kernels.h)
   bool no_fused_prep = false;  // PTZBA_NO_FUSED_PREP (A/B knob, read at set_problem)
-  bool fused_prep() const { return !no_fused_prep && !dist_mode && !has_exchange() && !ext_exchange && f1_covered; }
+  // Gaussian pose priors (ptzba_set_pose_priors; prior_kernels.hip PriorArgs): the device arrays of the current set.
+  // With priors set the build takes the separate prepare launch, which then sees diag P in dU.
+  struct Priors {
+    int n_factor = 0, n_row = 0, n_elem = 0, n_pframe = 0, n_block = 0;
+    DBuf f_begin, f_frames, f_mean, f_info_off, f_info, row_factor, s_off, s_val, p_frame, p_begin, p_ent, p_diag;
+    DBuf cost;  // [1] ptzba_pose_prior_info's read-back
+    DBuf red;   // [PRIOR_RED_SCRATCH] k_prior_cost's partials and counter (zeroed when allocated)
+  } pri;
+  std::vector<int32_t> win_host, pos_host;  // the problem's coupling window and system positions (prior validation)
+  bool has_priors() const { return pri.n_factor > 0; }
+  bool fused_prep() const {
+    return !no_fused_prep && !dist_mode && !has_exchange() && !ext_exchange && f1_covered && !has_priors();
+  }
   double* S() const { return sys.as<double>(); }
   double* bvec() const { return sys.as<double>() + ld * ld; }
   double* gpose() const { return sys.as<double>() + ld * ld + ld; }
@@ -265,7 +278,10 @@ const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.2 (round 6): ptzba_lm_opts carries huber_curvature / curvature_switch (11 fields; 0.1 had 9).  They are read
 // for the Huber loss only, and huber_curvature 0 means the default 0.1, so a zero-filled tail keeps 0.1's behaviour.
 // 0.3: ptzba_covariance / ptzba_cov_opts (sized by its struct_size field); ptzba_lm_opts as in 0.2.
-const char* ptzba_version(void) { return "ptzba 0.3 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance)"; }
+// 0.4: ptzba_set_pose_priors / ptzba_pose_priors (sized by struct_size) / ptzba_pose_prior_info.
+const char* ptzba_version(void) {
+  return "ptzba 0.4 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors)";
+}
 
 ptzba_handle ptzba_new(int device) {
   if (select_device(device)) return nullptr;
@@ -1464,6 +1480,7 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->st));
   h->have_problem = false;
+  h->pri.n_factor = 0;  // a new problem starts without pose priors
   h->ptz_saved.release();
   h->rays_saved.release();
   h->n_pose = n_pose;
@@ -1910,6 +1927,8 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   h->chol_delayed = plan.delayed;
   h->n_chain = (int)plan.chain_off.size() - 1;
   frame_win_hi = win;  // K2 windows follow the same (possibly global) coupling
+  h->win_host = win;
+  h->pos_host = sorder.pos;
   h->perm_uploaded = gpu_setup;  // (the device front wrote the permutation itself)
   if (gpu_setup) h->perm_host.clear();
 
@@ -2332,6 +2351,43 @@ static int ensure_group_comms(ptzba_ctx* h) {
   return 0;
 }
 
+// the handle's priors over the state pair (ptz, ptz_trial): sel == nullptr the host-driven pair (current = ptz), else
+// the device-driven LM's selection as in k_trial's sflip; flip = 1 picks the trial state instead of the current one
+static PriorArgs prior_args(const ptzba_ctx* h, const int* sel, int flip) {
+  const auto& p = h->pri;
+  PriorArgs a;
+  a.n_factor = p.n_factor;
+  a.n_row = p.n_row;
+  a.f_begin = p.f_begin.as<int32_t>();
+  a.f_frames = p.f_frames.as<int32_t>();
+  a.f_mean = p.f_mean.as<double>();
+  a.f_info_off = p.f_info_off.as<int64_t>();
+  a.f_info = p.f_info.as<double>();
+  a.row_factor = p.row_factor.as<int32_t>();
+  a.n_elem = p.n_elem;
+  a.s_off = p.s_off.as<int64_t>();
+  a.s_val = p.s_val.as<double>();
+  a.n_pframe = p.n_pframe;
+  a.p_frame = p.p_frame.as<int32_t>();
+  a.p_begin = p.p_begin.as<int32_t>();
+  a.p_ent = p.p_ent.as<int2>();
+  a.p_diag = p.p_diag.as<double>();
+  const double* cur = h->ptz.as<double>();
+  const double* oth = h->ptz_trial.as<double>();
+  if (sel) {
+    a.x0 = cur;
+    a.x1 = oth;
+    a.sel = sel;
+    a.sel_xor = h->state_base ^ flip;
+  } else {
+    a.x0 = flip ? oth : cur;
+    a.x1 = nullptr;
+    a.sel = nullptr;
+    a.sel_xor = 0;
+  }
+  return a;
+}
+
 int ptzba_linearize(ptzba_handle h) {
   if (!h || !h->have_problem) return fail("no problem set");
   HIPCHK(hipSetDevice(h->device));
@@ -2340,6 +2396,8 @@ int ptzba_linearize(ptzba_handle h) {
   linearize_into(h, h->cur);
   launch_reduce_cols(h->lm_out[h->cur].as<double>() + 5, h->n_lm, 8, 1, 0, h->scal.as<double>(),
                      h->red_scratch.as<double>(), h->st);
+  // scal[0], the cost at the current state, includes the prior (the reduction above stored the records' share)
+  if (h->has_priors()) launch_prior_cost(prior_args(h, nullptr, 0), h->scal.as<double>(), 1.0, 1, h->pri.red.as<double>(), h->st);
   HIPCHK(hipGetLastError());
   if (h->has_exchange()) return exchange(h, PTZBA_X_SCAL, h->scal.as<double>(), scal_count(h));
   return 0;
@@ -2387,6 +2445,10 @@ static int build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   else
     launch_schur<double>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, 0);
   tm_end(h, TM_SCHUR);
+  // pose priors: S += P, g_pose += P e, b -= P e, dU += diag P at the build's state (not part of the timed Schur group)
+  if (h->has_priors())
+    launch_prior_apply(prior_args(h, sel, 0), h->S(), h->bvec(), h->gpose(), h->dU(), h->frame_pos.as<int32_t>(), skip_if,
+                       h->st);
   HIPCHK(hipGetLastError());
   if (h->dist_mode) {
     if (!h->has_exchange()) return fail("a part-owned handle needs an exchange (ptzba_attach_comm / ptzba_set_exchange_hook)");
@@ -2506,6 +2568,9 @@ static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* se
     launch_trial<double>(b, h->ptz.as<double>(), h->gpose(), h->D_pose.as<double>(), h->ptz_trial.as<double>(),
                          h->locp(), h->n_pose, h->ft64.p, h->rt64.p, h->ft64.p, h->rt64.p, h->st, fm, finfo);
   tm_end(h, TM_BACK);
+  // the prior's cost at the trial state into loc[5], which the decision (host or device, fused or not) adds to the
+  // trial cost; without priors the slot stays zero
+  if (h->has_priors()) launch_prior_cost(prior_args(h, sel, 1), h->locp() + 5, 1.0, 0, h->pri.red.as<double>(), h->st);
   // trial linearisation (its cost decides acceptance; kept as the next linearisation if accepted).  Device-driven LM
   // with the huber curvature switch pending: single GPU (relin_mode 0), the trial's predicted reduction is reduced
   // first and picks the curvature of this linearisation (LMDev::hc_trial); ranks (relin_mode 1) use LMDev::hc
@@ -2776,7 +2841,7 @@ int ptzba_read_scalars(ptzba_handle h, double* out) {
   const double* s = h->scal_host;
   const double* l = h->scal_host + 8;
   out[0] = s[0];
-  out[1] = s[1];
+  out[1] = s[1] + l[5];  // l[5]: the pose priors' cost at the trial state (zero without priors)
   out[2] = s[2] + l[0];
   out[3] = s[3] + l[1];
   out[4] = s[4] + l[2];
@@ -2835,6 +2900,7 @@ int ptzba_unpack(ptzba_handle h) { return pack_impl(h, 1); }
 
 int ptzba_set_exchange_hook(ptzba_handle h, ptzba_exchange_fn fn, void* ctx) {
   if (!h) return fail("null handle");
+  if (fn && h->has_priors()) return fail("ptzba_set_exchange_hook: the handle has pose priors set (single rank only)");
   h->hook = fn;
   h->hook_ctx = ctx;
   return 0;
@@ -2842,6 +2908,7 @@ int ptzba_set_exchange_hook(ptzba_handle h, ptzba_exchange_fn fn, void* ctx) {
 
 int ptzba_attach_comm(ptzba_handle h, ptzba_comm comm) {
   if (!h) return fail("null handle");
+  if (comm && h->has_priors()) return fail("ptzba_attach_comm: the handle has pose priors set (single rank only)");
   h->drop_groups();
   h->comm = comm;
   return 0;  // the group communicator is split lazily by the first exchange (collective, every rank reaches it)
@@ -3489,6 +3556,153 @@ int ptzba_set_huber_curvature(ptzba_handle h, double hc) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Gaussian pose priors (include/ptzba.h ptzba_set_pose_priors; prior_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// Everything is validated on the host before the handle is touched.  P = sum_k Lambda_k is summed per unordered
+// frame pair in factor order (fp64) and resolved to elements of S's lower triangle through the system positions:
+// block (fa, fb) entry (q, r) lands where k_schur_reduce puts U / W V^-1 W^T of that pair, i.e. at row pos[fb] + r,
+// column pos[fa] + q when pos[fb] >= pos[fa] and transposed otherwise (the reversed part of a nested order).
+// Elements are addressed one by one, so a frame whose three rows straddle a 32-row tile needs no special case.
+int ptzba_set_pose_priors(ptzba_handle h, const ptzba_pose_priors* pr) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (pr && pr->struct_size != (int32_t)sizeof(ptzba_pose_priors))
+    return fail("ptzba_set_pose_priors: unknown struct_size %d of ptzba_pose_priors (this library knows %d)",
+                (int)pr->struct_size, (int)sizeof(ptzba_pose_priors));
+  HIPCHK(hipSetDevice(h->device));
+  if (!pr || pr->n_factor == 0) {
+    HIPCHK(hipStreamSynchronize(h->st));
+    h->pri.n_factor = 0;
+    HIPCHK(hipMemsetAsync(h->locp() + 5, 0, 8, h->st));  // the trial-cost slot of the decisions
+    return 0;
+  }
+  if (h->dist_mode || h->dist_world > 1 || h->has_exchange() || h->ext_exchange || h->scal_exported)
+    return fail("ptzba_set_pose_priors: single rank only (the handle is sharded, has a communicator / hook attached "
+                "or runs a caller-side exchange)");
+  const int nF = pr->n_factor;
+  if (nF < 0 || !pr->factor_begin || !pr->frames || !pr->mean || !pr->info)
+    return fail("ptzba_set_pose_priors: bad arguments (n_factor %d, null array)", nF);
+  if (pr->factor_begin[0] != 0) return fail("ptzba_set_pose_priors: factor_begin[0] must be 0");
+  std::vector<int32_t> f_begin(pr->factor_begin, pr->factor_begin + nF + 1), row_factor;
+  std::vector<int64_t> info_off(nF);
+  int64_t n_info = 0;
+  for (int k = 0; k < nF; ++k) {
+    const int G = f_begin[k + 1] - f_begin[k];
+    if (G < 1 || G > 8) return fail("ptzba_set_pose_priors: factor %d names %d frames (1..8 allowed)", k, G);
+    info_off[k] = n_info;
+    n_info += (int64_t)9 * G * G;
+  }
+  const int n_fr = f_begin[nF];
+  std::vector<int32_t> frames(pr->frames, pr->frames + n_fr);
+  std::vector<double> mean(pr->mean, pr->mean + 3 * (size_t)n_fr), info(pr->info, pr->info + n_info);
+  std::map<std::pair<int, int>, std::array<double, 9>> blocks;  // (fa <= fb) -> P block, rows fa, columns fb
+  std::map<int, std::vector<int2>> by_frame;                    // frame -> (factor, slot), factor order
+  for (int k = 0; k < nF; ++k) {
+    const int f0 = f_begin[k], G = f_begin[k + 1] - f0, n3 = 3 * G;
+    for (int a = 0; a < G; ++a) {
+      const int f = frames[f0 + a];
+      if (f < h->n_fixed || f >= h->n_pose)
+        return fail("ptzba_set_pose_priors: factor %d names frame %d, not a free frame [%d, %d)", k, f, h->n_fixed, h->n_pose);
+      for (int c = 0; c < a; ++c)
+        if (frames[f0 + c] == f) return fail("ptzba_set_pose_priors: factor %d names frame %d twice", k, f);
+    }
+    double* L = info.data() + info_off[k];
+    double amax = 0.0;
+    for (int e = 0; e < n3 * n3; ++e) {
+      if (!std::isfinite(L[e])) return fail("ptzba_set_pose_priors: factor %d: non-finite information entry", k);
+      amax = std::max(amax, std::fabs(L[e]));
+    }
+    for (int e = 0; e < n3; ++e) {
+      if (!std::isfinite(mean[3 * (size_t)f0 + e])) return fail("ptzba_set_pose_priors: factor %d: non-finite mean", k);
+      if (L[e * n3 + e] < 0.0)
+        return fail("ptzba_set_pose_priors: factor %d: negative diagonal entry %g of the information matrix", k, L[e * n3 + e]);
+    }
+    for (int i = 0; i < n3; ++i)
+      for (int j = 0; j < i; ++j) {
+        if (std::fabs(L[i * n3 + j] - L[j * n3 + i]) > 1e-12 * amax)
+          return fail("ptzba_set_pose_priors: factor %d: information matrix not symmetric (entries %d,%d differ by %g)", k,
+                      i, j, std::fabs(L[i * n3 + j] - L[j * n3 + i]));
+        L[i * n3 + j] = L[j * n3 + i] = 0.5 * (L[i * n3 + j] + L[j * n3 + i]);
+      }
+    for (int a = 0; a < G; ++a)
+      for (int c = 0; c < G; ++c) {
+        const int fa = frames[f0 + a], fb = frames[f0 + c];
+        if (fa < fb && fb > h->win_host[fa])
+          return fail("ptzba_set_pose_priors: factor %d couples frames %d and %d, but the handle's coupling window of "
+                      "frame %d ends at %d: pass frame_win_hi[%d] >= %d to ptzba_set_problem", k, fa, fb, fa,
+                      h->win_host[fa], fa, fb);
+        if (fa > fb) continue;  // the pair's block is summed from its (lower frame, higher frame) side
+        auto it = blocks.find({fa, fb});
+        if (it == blocks.end()) it = blocks.emplace(std::make_pair(fa, fb), std::array<double, 9>{}).first;
+        for (int q = 0; q < 3; ++q)
+          for (int r = 0; r < 3; ++r) it->second[3 * q + r] += L[(3 * a + q) * n3 + 3 * c + r];
+      }
+    for (int a = 0; a < G; ++a) by_frame[frames[f0 + a]].push_back(make_int2(k, a));
+    for (int e = 0; e < n3; ++e) row_factor.push_back(k);
+  }
+  std::vector<int64_t> s_off;
+  std::vector<double> s_val;
+  const int64_t ld = h->ld;
+  for (const auto& kv : blocks) {
+    const int fa = kv.first.first, fb = kv.first.second;
+    const int64_t pa = h->pos_host[fa], pb = h->pos_host[fb];
+    if (pa < 0 || pb < 0 || pa + 2 >= h->n_aug || pb + 2 >= h->n_aug)
+      return fail("ptzba_set_pose_priors: frames %d / %d lie outside the reduced system", fa, fb);
+    for (int q = 0; q < 3; ++q)
+      for (int r = 0; r < 3; ++r) {
+        s_off.push_back(pb >= pa ? (pb + r) * ld + pa + q : (pa + q) * ld + pb + r);
+        s_val.push_back(kv.second[3 * q + r]);
+      }
+  }
+  std::vector<int32_t> p_frame, p_begin{0};
+  std::vector<int2> p_ent;
+  std::vector<double> p_diag;
+  for (const auto& kv : by_frame) {
+    p_frame.push_back(kv.first);
+    p_ent.insert(p_ent.end(), kv.second.begin(), kv.second.end());
+    p_begin.push_back((int32_t)p_ent.size());
+    const auto& d = blocks.at({kv.first, kv.first});
+    p_diag.insert(p_diag.end(), {d[0], d[4], d[8]});
+  }
+  // queued work may still read the previous set's arrays
+  HIPCHK(hipStreamSynchronize(h->st));
+  auto& p = h->pri;
+  p.n_factor = 0;
+  if (!p.red.p) {
+    if (p.red.alloc(PRIOR_RED_SCRATCH * 8)) return -1;
+    HIPCHK(hipMemsetAsync(p.red.p, 0, PRIOR_RED_SCRATCH * 8, h->st));
+  }
+  if (upload(p.f_begin, f_begin, h->st) || upload(p.f_frames, frames, h->st) || upload(p.f_mean, mean, h->st) ||
+      upload(p.f_info_off, info_off, h->st) || upload(p.f_info, info, h->st) || upload(p.row_factor, row_factor, h->st) ||
+      upload(p.s_off, s_off, h->st) || upload(p.s_val, s_val, h->st) || upload(p.p_frame, p_frame, h->st) ||
+      upload(p.p_begin, p_begin, h->st) || upload(p.p_ent, p_ent, h->st) || upload(p.p_diag, p_diag, h->st))
+    return -1;
+  p.n_row = 3 * n_fr;
+  p.n_elem = (int)s_off.size();
+  p.n_pframe = (int)p_frame.size();
+  p.n_block = (int)blocks.size();
+  p.n_factor = nF;
+  return 0;
+}
+
+int ptzba_pose_prior_info(ptzba_handle h, double* out4) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!out4) return fail("ptzba_pose_prior_info: null output");
+  const auto& p = h->pri;
+  out4[0] = p.n_factor;
+  out4[1] = p.n_factor ? p.n_row : 0;
+  out4[2] = p.n_factor ? p.n_block : 0;
+  out4[3] = 0.0;
+  if (!h->has_priors()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->pri.cost.p && h->pri.cost.alloc(8)) return -1;
+  launch_prior_cost(prior_args(h, nullptr, 0), h->pri.cost.as<double>(), 1.0, 0, h->pri.red.as<double>(), h->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out4 + 3, h->pri.cost.p, 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // posterior covariance: diagonal blocks of scale * H^-1 at the current state (cov_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 // the covariance plan of the current problem, from the device copies of the solver's own structure (a solve keeps no
@@ -3588,9 +3802,10 @@ int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* o, double* pose_cov, 
   if (cov_prepare(h)) return -1;
   auto& c = h->cov;
   const int n_free = 3 * (h->n_pose - h->n_fixed) + 2 * c.n_active;
-  const double dof = 2.0 * (double)h->n_rec - (double)n_free;
+  // pose priors: every prior row counts as a residual (rank-deficient factors over-count, include/ptzba.h)
+  const double dof = 2.0 * (double)h->n_rec + (h->has_priors() ? (double)h->pri.n_row : 0.0) - (double)n_free;
   if (opt.scale_mode == 2 && !(dof > 0)) return fail("ptzba_covariance: residual scale needs more residuals (%lld) than "
-                                                     "free parameters (%d)", (long long)(2 * h->n_rec), n_free);
+                                                     "free parameters (%d)", (long long)(2 * h->n_rec + (h->has_priors() ? h->pri.n_row : 0)), n_free);
   const int n_ray_blocks = (int)((n_sel + CHOL_NB / 2 - 1) / (CHOL_NB / 2));
   const int n_pose_blocks = pose_cov ? c.n_pose_blocks : 0;
   const int n_groups = std::min(c.max_groups, n_pose_blocks + n_ray_blocks);
@@ -3630,6 +3845,8 @@ int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* o, double* pose_cov, 
                                h->rt64.p, h->u, h->v, h->n_rec, h->loss == PTZBA_LOSS_HUBER, h->fs, resid + 8, n_part,
                                resid, h->st);
   }
+  // ... + sum_k e_k^T Lambda_k e_k, twice the prior cost
+  if (opt.scale_mode == 2 && h->has_priors()) launch_prior_cost(prior_args(h, nullptr, 0), resid, 2.0, 1, h->pri.red.as<double>(), h->st);
   if (build_impl(h, 0.0, nullptr) || factor_impl(h, nullptr, nullptr)) return -1;
   HIPCHK(hipMemcpyAsync(h->D_pose.p, dsave, h->D_pose.bytes, hipMemcpyDeviceToDevice, h->st));
   HIPCHK(hipMemcpyAsync(h->D_ray.p, dsave + h->D_pose.bytes / 8, h->D_ray.bytes, hipMemcpyDeviceToDevice, h->st));

@@ -956,7 +956,8 @@ __device__ void lm_decide_body(LMDev* st, const double* scal, const double* __re
   s.relin = 0;
   if (!s.done) {
     const LMParams& p = s.p;
-    const double new_cost = scal[1], pred = scal[2] + loc[0], dx2 = scal[3] + loc[1], x2 = scal[4] + loc[2];
+    // loc[5]: the pose priors' cost at the trial state (k_prior_cost, launched after k_trial); zero without priors
+    const double new_cost = scal[1] + loc[5], pred = scal[2] + loc[0], dx2 = scal[3] + loc[1], x2 = scal[4] + loc[2];
     const double gmax = fmax(loc[3], scal[5]);  // free poses (k_trial's pose block) | rays (lm_red column 3)
     s.nfev += 1;
     s.trials += 1;

@@ -358,6 +358,45 @@ void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const in
                       const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
                       int64_t n_rec, int huber, double f_scale, double* part, int n_part, double* out, hipStream_t st);
 
+// Gaussian pose priors (prior_kernels.hip; ptzba_set_pose_priors): factor k names G_k free frames, a mean and a
+// symmetric information matrix Lambda_k over their 3 G_k pose parameters; cost += 1/2 sum_k e_k^T Lambda_k e_k,
+// e_k = x_{F_k} - mean_k.  The host resolves P = sum_k Lambda_k to elements of the lower triangle of S once per
+// set call; the device forms e from the current state in fp64.
+struct PriorArgs {
+  int n_factor;
+  int n_row;                   // sum_k 3 G_k
+  const int32_t* f_begin;      // [n_factor + 1] CSR of the factors' frames
+  const int32_t* f_frames;     // [n_row / 3]
+  const double* f_mean;        // [n_row], 3 per listed frame
+  const int64_t* f_info_off;   // [n_factor] first entry of the factor's (3G)^2 block in f_info
+  const double* f_info;        // row-major blocks, symmetrised
+  const int32_t* row_factor;   // [n_row] factor of each prior row (cost kernel)
+  int n_elem;                  // elements of P in S
+  const int64_t* s_off;        // [n_elem] offset into S (lower triangle, system order)
+  const double* s_val;         // [n_elem] pre-summed in factor order
+  int n_pframe;                // distinct frames under a prior
+  const int32_t* p_frame;      // [n_pframe] ascending
+  const int32_t* p_begin;      // [n_pframe + 1] CSR of the (factor, slot) pairs naming the frame, factor order
+  const int2* p_ent;
+  const double* p_diag;        // [3 n_pframe] diag P
+  // the state e is formed from: x0, or x1 when sel != nullptr and ((*sel) ^ sel_xor) is odd (device-driven LM:
+  // the pair k_trial's sflip selects; the trial cost passes the xor flipped)
+  const double* x0;
+  const double* x1;
+  const int* sel;
+  int sel_xor;
+};
+// S += P, g_pose += Lambda e, b -= Lambda e (k_schur_reduce's b = -g + ...), dU += diag P; one thread per written
+// element, no atomics.  skip_if as the build's launches.
+void launch_prior_apply(const PriorArgs& a, double* S, double* b, double* g_pose, double* dU,
+                        const int32_t* frame_pos, const int* skip_if, hipStream_t st);
+// c = 1/2 sum_k e^T Lambda e at the selected state (fixed-order sum over up to PRIOR_RED_BLOCKS workgroups): out[0] =
+// mul * c, or out[0] += mul * c with accumulate != 0.  scratch: PRIOR_RED_SCRATCH doubles (partials + counter),
+// zero-initialised once, reused by every launch on the handle's stream
+constexpr int PRIOR_RED_BLOCKS = 64;
+constexpr int PRIOR_RED_SCRATCH = PRIOR_RED_BLOCKS + 2;
+void launch_prior_cost(const PriorArgs& a, double* out, double mul, int accumulate, double* scratch, hipStream_t st);
+
 // camera batch kernels (camera_kernels.hip)
 void launch_ray_to_image(int64_t n, double u, double v, const double* f, const double* cp, const double* ct,
                          const double* th, const double* ph, double* x, double* y, hipStream_t st);

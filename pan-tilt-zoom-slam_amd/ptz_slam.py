@@ -46,6 +46,9 @@ class PtzSlam:
         self.angle_var = 0.001
         self.f_var = 1
         self.device = ptzba.default_device()
+        # True: a new keyframe enters the map's bundle adjustment with the tracker's pose covariance
+        # (state_cov[:3, :3]) as a Gaussian prior on its pose (Map.add_keyframe_with_ba pose_prior)
+        self.keyframe_prior = False
 
     # ------------------------------------------------------------------ device-backed state
     @property
@@ -257,5 +260,7 @@ class PtzSlam:
             if frame_index == 0:
                 self.keyframe_map.add_first_keyframe(new_keyframe, verbose=True)
             else:
-                self.keyframe_map.add_keyframe_with_ba(new_keyframe, "./bundle_result/", verbose=True)
+                prior = np.array(self.state_cov[:3, :3], dtype=np.float64) if self.keyframe_prior else None
+                self.keyframe_map.add_keyframe_with_ba(new_keyframe, "./bundle_result/", verbose=True,
+                                                       **({} if prior is None else {"pose_prior": prior}))
                 self.new_keyframe = False

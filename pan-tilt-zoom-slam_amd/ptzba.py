@@ -77,6 +77,15 @@ class ptzba_cov_opts(Structure):
 COV_SCALE_UNIT, COV_SCALE_GIVEN, COV_SCALE_RESIDUAL = 0, 1, 2
 
 
+class ptzba_pose_priors(Structure):
+    """include/ptzba.h ptzba_pose_priors; struct_size = ctypes.sizeof(ptzba_pose_priors)."""
+    _fields_ = [("struct_size", c_int32), ("n_factor", c_int32), ("factor_begin", c_void_p), ("frames", c_void_p),
+                ("mean", c_void_p), ("info", c_void_p)]
+
+
+PRIOR_MAX_FRAMES = 8  # frames one prior factor may name (include/ptzba.h)
+
+
 class ptzba_report(Structure):
     _fields_ = [("cost", c_double), ("initial_cost", c_double), ("time_s", c_double), ("iterations", c_int32),
                 ("nfev", c_int32), ("trials", c_int32), ("status", c_int32)]
@@ -134,6 +143,8 @@ def lib():
         "ptzba_step": ([V, D], I),
         "ptzba_set_huber_curvature": ([V, D], I),
         "ptzba_covariance": ([V, POINTER(ptzba_cov_opts), V, V, I32, V, V], I),
+        "ptzba_set_pose_priors": ([V, POINTER(ptzba_pose_priors)], I),
+        "ptzba_pose_prior_info": ([V, V], I),
         "ptzba_set_setup_front": ([V, I64], I),
         "ptzba_setup_timing": ([V, I32, V, V, V], I),
         "ptzba_solve": ([V, V, V, POINTER(ptzba_lm_opts), POINTER(ptzba_report)], I),
@@ -240,6 +251,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_plan_export", "ptzba_dist_exchanges", "ptzba_dist_groups", "ptzba_exchange_group", "ptzba_dist_plan_summary",
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
+    "ptzba_set_pose_priors", "ptzba_pose_prior_info",
 ]
 
 
@@ -738,6 +750,58 @@ def frame_coupling_window(n_pose, frame, landmark):
     return win
 
 
+def check_pose_priors(factors, n_pose=None):
+    """Validate a prior factor list [(frames, mean, info), ...] on the host and return it as
+    [(frames int32 [G], mean float64 [3 G], info float64 [3 G, 3 G])]: factor k puts the Gaussian prior
+    1/2 e^T info e, e = x[frames] - mean, on the poses of its G distinct frames (1 <= G <= 8; per frame pan, tilt, f).
+    ValueError for a bad shape, a repeated frame, a non-finite value or an info matrix that is not symmetric positive
+    semi-definite (an eigenvalue below -1e-12 max|info|)."""
+    out = []
+    for k, fac in enumerate(factors):
+        try:
+            frames, mean, info = fac
+        except (TypeError, ValueError):
+            raise ValueError(f"prior factor {k}: expected (frames, mean, info)")
+        frames = np.atleast_1d(np.asarray(frames))
+        if frames.ndim != 1 or not np.issubdtype(frames.dtype, np.integer):
+            raise ValueError(f"prior factor {k}: frames must be a 1-d integer list")
+        G = len(frames)
+        if not 1 <= G <= PRIOR_MAX_FRAMES:
+            raise ValueError(f"prior factor {k}: {G} frames (1..{PRIOR_MAX_FRAMES} allowed)")
+        if len(set(frames.tolist())) != G:
+            raise ValueError(f"prior factor {k}: a frame is repeated")
+        if frames.min() < 0 or (n_pose is not None and frames.max() >= n_pose):
+            raise ValueError(f"prior factor {k}: frame out of range")
+        mean = np.asarray(mean, np.float64)
+        info = np.asarray(info, np.float64)
+        if mean.size != 3 * G or info.shape != (3 * G, 3 * G):
+            raise ValueError(f"prior factor {k}: mean needs {3 * G} values and info shape ({3 * G}, {3 * G}); "
+                             f"got {mean.shape} and {info.shape}")
+        if not (np.isfinite(mean).all() and np.isfinite(info).all()):
+            raise ValueError(f"prior factor {k}: non-finite value")
+        amax = float(np.abs(info).max())
+        if np.abs(info - info.T).max() > 1e-12 * amax:
+            raise ValueError(f"prior factor {k}: info is not symmetric")
+        if amax > 0 and np.linalg.eigvalsh(0.5 * (info + info.T)).min() < -1e-12 * amax:
+            raise ValueError(f"prior factor {k}: info is not positive semi-definite")
+        out.append((np.ascontiguousarray(frames, np.int32), np.ascontiguousarray(mean.reshape(-1)),
+                    np.ascontiguousarray(info)))
+    return out
+
+
+def prior_window(n_pose, frame, landmark, factors):
+    """frame_coupling_window of the records, raised so that every frame pair of every prior factor is covered: the
+    `frame_win_hi` to pass to set_problem before set_pose_priors (the factor pattern of the reduced system then holds
+    the tiles the prior's blocks land in)."""
+    win = frame_coupling_window(n_pose, frame, landmark).copy()
+    for frames, _, _ in factors:
+        fr = np.atleast_1d(np.asarray(frames)).astype(np.int64)
+        hi = int(fr.max())
+        for f in fr:
+            win[f] = max(win[f], hi)
+    return win
+
+
 def plan_summary(frame_win_hi, n_fixed=1, ordering=None):
     """The system order and factorisation plan ptzba_set_problem would choose for a coupling window
     (ptzba_plan_summary, host only): dict(n_aug, ld, levels, nd_depth, chains, longest_chain, bs_steps,
@@ -1175,6 +1239,31 @@ class BAHandle:
                                       _ptr(info)), "ptzba_covariance")
         return pose_cov, ray_cov, dict(scale=float(info[0]), min_pivot=float(info[1]), n_free=int(info[2]),
                                        device_ms=float(info[3]))
+
+    def set_pose_priors(self, factors):
+        """Gaussian pose priors (ptzba_set_pose_priors): factors = [(frames, mean, info), ...], see check_pose_priors.
+        Valid after set_problem, between solves; an empty list clears them.  A factor pair outside the handle's coupling
+        window is refused (PtzbaError): pass prior_window(...) as set_problem's frame_win_hi."""
+        facs = check_pose_priors(factors, self.n_pose)
+        if not facs:
+            return self.clear_pose_priors()
+        begin = np.zeros(len(facs) + 1, np.int32)
+        begin[1:] = np.cumsum([len(f[0]) for f in facs])
+        frames = np.ascontiguousarray(np.concatenate([f[0] for f in facs]), np.int32)
+        mean = np.ascontiguousarray(np.concatenate([f[1] for f in facs]))
+        info = np.ascontiguousarray(np.concatenate([f[2].reshape(-1) for f in facs]))
+        pr = ptzba_pose_priors(ctypes.sizeof(ptzba_pose_priors), len(facs), _ptr(begin).value, _ptr(frames).value,
+                               _ptr(mean).value, _ptr(info).value)
+        _check(lib().ptzba_set_pose_priors(self.h, ctypes.byref(pr)), "ptzba_set_pose_priors")
+
+    def clear_pose_priors(self):
+        _check(lib().ptzba_set_pose_priors(self.h, None), "ptzba_set_pose_priors")
+
+    def pose_prior_info(self):
+        """(factors, prior rows sum 3 G, distinct 3 x 3 blocks of P, prior cost at the current state)."""
+        out = np.zeros(4)
+        _check(lib().ptzba_pose_prior_info(self.h, _ptr(out)), "ptzba_pose_prior_info")
+        return int(out[0]), int(out[1]), int(out[2]), float(out[3])
 
     def build_reduced(self, lam):
         _check(lib().ptzba_build_reduced(self.h, float(lam)), "ptzba_build_reduced")
@@ -1625,19 +1714,26 @@ def _cov_kwargs(covariance):
 
 
 def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, weight=None, precision=FP64,
-          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, **lm_kw):
+          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, pose_priors=None, **lm_kw):
     """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
     BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
     (pose_cov, ray_cov, info) at the solution.  keep_handle=True (default): one
     handle per device is kept between calls (a keyframe map solves on every new keyframe: creating and
     destroying a handle -- stream, pinned records, device buffers -- cost ~6 ms per call); set_problem replaces
     its problem and release_solve_handles() frees it.  keep_handle=False: a private handle, closed on return.
-    The shared handle is used under a lock: concurrent callers on one device run one at a time."""
+    The shared handle is used under a lock: concurrent callers on one device run one at a time.
+    pose_priors: a prior factor list (BAHandle.set_pose_priors); the coupling window is raised for it (prior_window)."""
+    win = None
+    if pose_priors:
+        pose_priors = check_pose_priors(pose_priors, n_pose)
+        win = prior_window(n_pose, frame, landmark, pose_priors)
     if not keep_handle:
         h = BAHandle(device)
         try:
             h.set_problem(n_pose, n_landmark, frame, landmark, xy, u, v, weight=weight, precision=precision, loss=loss,
-                          f_scale=f_scale)
+                          f_scale=f_scale, frame_win_hi=win)
+            if pose_priors:
+                h.set_pose_priors(pose_priors)
             h.set_state(init_ptz, init_rays)
             res = LMSolver(h, **lm_kw).run()
             ptz, rays = h.get_state()
@@ -1655,7 +1751,9 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
         try:
             t0 = time.perf_counter()
             h.set_problem(n_pose, n_landmark, frame, landmark, xy, u, v, weight=weight, precision=precision, loss=loss,
-                          f_scale=f_scale)
+                          f_scale=f_scale, frame_win_hi=win)
+            if pose_priors:
+                h.set_pose_priors(pose_priors)
             t1 = time.perf_counter()
             h.set_state(init_ptz, init_rays)
             t2 = time.perf_counter()

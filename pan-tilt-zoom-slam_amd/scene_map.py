@@ -50,10 +50,21 @@ class Map:
         assert isinstance(keyframe, KeyFrame)
         self.keyframe_list.append(keyframe)
 
-    def add_keyframe_with_ba(self, keyframe, save_path, verbose=False):
-        """scene_map.py:53-117: append, BA over all keyframes, keep keyframes with features."""
+    def add_keyframe_with_ba(self, keyframe, save_path, verbose=False, pose_prior=None):
+        """scene_map.py:53-117: append, BA over all keyframes, keep keyframes with features.
+        pose_prior: optional 3 x 3 covariance (pan, tilt, f) of the new keyframe's pose, e.g. the tracker's; the BA then
+        carries the Gaussian prior with that covariance around the keyframe's current pose (bundle_adjustment's
+        pose_priors)."""
         assert isinstance(keyframe, KeyFrame)
         assert len(self.keyframe_list) >= 1
+        prior_kw = {}
+        if pose_prior is not None:
+            cov = np.asarray(pose_prior, np.float64)
+            if cov.shape != (3, 3) or not np.isfinite(cov).all() or np.linalg.eigvalsh(0.5 * (cov + cov.T)).min() <= 0:
+                raise ValueError("pose_prior must be a positive definite 3 x 3 covariance")
+            info = np.linalg.inv(0.5 * (cov + cov.T))
+            prior_kw = dict(pose_priors=[([keyframe.img_index], [keyframe.pan, keyframe.tilt, keyframe.f],
+                                          0.5 * (info + info.T))])
         ref = self.keyframe_list[0]
         self.add_keyframe_without_ba(keyframe, False)
         kept = []
@@ -69,7 +80,7 @@ class Map:
         start = time.time()
         landmarks, keyframes = bundle_adjustment(images, image_indices, self.feature_method, initial_ptzs, ref.center,
                                                  ref.base_rotation, ref.u, ref.v, save_path, verbose,
-                                                 correspondences=self.correspondences, **self.ba_options)
+                                                 correspondences=self.correspondences, **self.ba_options, **prior_kw)
         end = time.time()
         self.keyframe_list.pop()
         self.global_ray = landmarks
