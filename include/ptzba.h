@@ -322,6 +322,73 @@ PTZBA_EXPORT int ptzba_set_pose_priors(ptzba_handle h, const ptzba_pose_priors* 
 /* out4: [0] factors, [1] prior rows sum_k 3 G_k, [2] distinct 3 x 3 blocks of P (unordered frame pairs, the diagonal
  * ones included), [3] the prior cost 1/2 sum_k e_k^T Lambda_k e_k at the handle's current state (0 without priors) */
 PTZBA_EXPORT int ptzba_pose_prior_info(ptzba_handle h, double* out4);
+
+/* Marginalisation of keyframes that leave a sliding window (ptzba_version 0.5).
+ *
+ * ptzba_marginal_prior turns the records named by drop_mask (one byte per record, ptzba_set_problem's record order;
+ * non-zero = dropped) and the leaving frames E = drop_frames into one dense information-form factor over the frame
+ * set K: the free frames outside E that carry a dropped record or are named by an absorbed factor, ascending.
+ * Everything is linearised at the handle's current state x (Huber rows scaled by sqrt(rho'), curvature 1).  The
+ * landmarks of the dropped records are treated as independent copies, linearised at the current ray and eliminated
+ * with the dropped records only, so no kept observation is counted twice:
+ *     S_D = U_D - sum_l W_l V_l^-1 W_l^T,   b_D = g_p - sum_l W_l V_l^-1 g_l      (dropped records only)
+ *     A = S_D(K u E) + sum_absorbed Lambda_k,   a = b_D(K u E) + sum_absorbed (Lambda_k e_k [+ eta_k])
+ *     info = A_KK - A_KE A_EE^-1 A_EK,   grad = a_K - A_KE A_EE^-1 a_E,   lin = x_K
+ *     offset = 1/2 sum_D rho(r^2) + the absorbed factors' cost at x
+ * and the factor stands for q(x) = offset + grad^T d + 1/2 d^T info d, d = x_K - lin.  A factor is absorbed (whole;
+ * its other frames join K) when it names a free frame of E: pose-prior factors and the handle's marginal factor.
+ * Fixed frames of E (< n_fixed) have no columns.  info is positive semi-definite and generally singular.
+ *
+ * Outputs: frames_out[cap] / *n_out the frames of K; lin_out [3 n], info_out [3 n x 3 n] row-major, grad_out [3 n],
+ * *offset_out.  With frames_out == NULL only *n_out is written (size query).  stats may be NULL.
+ * Between solves, single rank.  The call borrows the handle's linearisation and leaves the handle as ptzba_linearize
+ * does (Marquardt scales, damping and huber curvature setting restored, as ptzba_covariance): a solve started
+ * afterwards takes bitwise the steps it takes without the call.
+ * Refused with a message, the handle left as it was: an unknown struct_size; a frame out of range or repeated; n_mask
+ * != the problem's record count; no record dropped and nothing absorbed; more than 8 free frames in E or more than
+ * 64 frames in K; cap < |K|; a pending LM trial; a sharded handle or one with a communicator / hook attached; a
+ * pivot of A_EE <= pivot_tol x its largest diagonal entry (the dropped terms do not determine that frame; the
+ * message names it). */
+typedef struct {
+  int32_t struct_size; /* sizeof(ptzba_marg_opts) */
+  int32_t reserved;    /* 0 */
+  double pivot_tol;    /* 0: the default 1e-13 */
+} ptzba_marg_opts;
+typedef struct {
+  int32_t struct_size;        /* sizeof(ptzba_marg_stats), set by the caller */
+  int32_t marginal_absorbed;  /* 1: the handle's marginal factor was absorbed */
+  int64_t dropped_records;
+  int64_t dropped_landmarks;
+  int32_t n_absorbed;         /* pose-prior factors absorbed */
+  int32_t absorbed_cap;       /* in: entries of absorbed[] */
+  int32_t* absorbed;          /* out: their indices, ascending (the first absorbed_cap of them); may be NULL */
+  double min_pivot;           /* smallest Cholesky pivot of A_EE (0 with no free frame in E) */
+  double device_ms;
+} ptzba_marg_stats;
+#define PTZBA_MARG_MAX_DROP 8
+#define PTZBA_MARG_MAX_FRAMES 64
+PTZBA_EXPORT int ptzba_marginal_prior(ptzba_handle h, const ptzba_marg_opts* opts, const int32_t* drop_frames,
+                                      int32_t n_drop, const uint8_t* drop_mask, int64_t n_mask, int32_t cap,
+                                      int32_t* frames_out, int32_t* n_out, double* lin_out, double* info_out,
+                                      double* grad_out, double* offset_out, ptzba_marg_stats* stats);
+/* One dense information-form factor q(x) = offset + grad^T d + 1/2 d^T info d, d = x_F - lin, next to (and separate
+ * from) the ptzba_set_pose_priors list: every solve path, cost, gradient and ptzba_covariance include it as they
+ * include the pose priors (ptzba_covariance's residual scale does not count it).  Validation and persistence as
+ * ptzba_set_pose_priors: free distinct frames, 1..64; finite values; a non-negative diagonal; asymmetry within 1e-12
+ * max|info| symmetrised, more refused; every pair inside the coupling window; copied; cleared by ptzba_set_problem,
+ * or by NULL / n_frame == 0. */
+typedef struct {
+  int32_t struct_size; /* sizeof(ptzba_marginal) */
+  int32_t n_frame;
+  const int32_t* frames; /* [n_frame] */
+  const double* lin;     /* [3 n_frame] */
+  const double* info;    /* [3 n_frame x 3 n_frame] row-major */
+  const double* grad;    /* [3 n_frame] */
+  double offset;
+} ptzba_marginal;
+PTZBA_EXPORT int ptzba_set_marginal_prior(ptzba_handle h, const ptzba_marginal* m);
+/* out4: [0] frames, [1] rows, [2] offset, [3] q(x) at the handle's current state (0 without a marginal) */
+PTZBA_EXPORT int ptzba_marginal_prior_info(ptzba_handle h, double* out4);
 /* Which front builds the record arrays in the following ptzba_set_problem calls of this handle (round 6): the device
  * front (one rocPRIM radix sort + segment / record kernels) from min_records records on, the host's counting sorts
  * below.  0: always the device, INT64_MAX: never, -1: the default (64K records since round 6, 4M before: configs 3 and 4

@@ -124,7 +124,8 @@ class _KeyframeLists:
 
 def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, center, rotation, u, v, save_path,
                       verbose=False, precision="fp64", loss="linear", f_scale=1.0, ftol=1e-4, xtol=1e-8,
-                      max_iter=100, device=0, correspondences=None, *, covariance=False, pose_priors=None):
+                      max_iter=100, device=0, correspondences=None, *, covariance=False, pose_priors=None,
+                      marginal_prior=None, marginalize=None):
     """bundle_adjustment.py:109-251 on the MI355X path.  Returns (landmarks [M,2], keyframes).
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
@@ -134,6 +135,12 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     [(image indices, mean, info), ...] keyed by image index (entries of image_indices) -- ptzba.check_pose_priors'
     factor form, 1/2 e^T info e with e = the named images' (pan, tilt, f) minus mean, added to the objective.  A factor
     on the call's first image (the gauge, held fixed) or on an image that is not part of the call raises ValueError.
+    marginal_prior (keyword only; off: the call and its outputs are unchanged): a ptzba.Marginal keyed by image index,
+    the information-form factor earlier calls' marginalize= produced (merged / conditioned by the caller); the gauge
+    image is conditioned at its held pose.  A key that is not an image of the call raises ValueError.
+    marginalize (keyword only): a list of image indices that are about to leave the window -- the returned tuple gains
+    a last element {"marginal": ptzba.Marginal keyed by image index (None without records), "stats": dict}, the
+    marginal of those images' matches at the returned solution (ptzba.BAHandle.marginal_prior).
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
@@ -156,6 +163,18 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
                 raise ValueError(f"pose prior {n}: image {image_indices[0]} is the gauge frame (held fixed)")
             priors.append(([where[k] for k in keys], mean, info))
         priors = ptzba.check_pose_priors(priors, N)
+    where = {k: i for i, k in enumerate(image_indices)}
+    marg = None
+    if marginal_prior is not None and len(marginal_prior.frames):
+        if any(int(k) not in where for k in marginal_prior.frames):
+            raise ValueError("marginal_prior: image index not among image_indices")
+        marg = marginal_prior.reindex(where)
+    leaving = None
+    if marginalize is not None:
+        keys = np.atleast_1d(np.asarray(marginalize)).tolist()
+        if any(k not in where for k in keys):
+            raise ValueError("marginalize: image index not among image_indices")
+        leaving = [where[k] for k in keys]
     timing = {}
     t_start = time.time()
 
@@ -204,14 +223,18 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     all_poses = initial_ptzs.copy()
     landmarks = rays0.copy()
     res = None
+    marg_out = dict(marginal=None, stats={})  # (no records: nothing to marginalise)
     cov = dict(pose_cov=np.zeros((N, 3, 3)), ray_cov=np.zeros((n_landmark, 2, 2)), info={})  # (no records: no blocks)
     if len(frame):
         prec = ptzba.FP32 if precision == "fp32" else ptzba.FP64
         ls = ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
-                          covariance=True if covariance else None, pose_priors=priors)
+                          covariance=True if covariance else None, pose_priors=priors, marginal_prior=marg,
+                          marginalize=leaving)
         all_poses, landmarks, res = out[:3]
+        if leaving is not None:
+            marg_out = dict(marginal=out[-1]["marginal"].reindex(dict(enumerate(image_indices))), stats=out[-1]["stats"])
         if covariance:
             cov = dict(pose_cov=out[3][0], ray_cov=out[3][1], info=out[3][2])
         all_poses[0] = ref_pose
@@ -238,6 +261,5 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     LAST_RESULT.clear()
     LAST_RESULT.update(result=res, n_residual=n_residual, n_landmark=n_landmark, time=timing["solve"],
                        timing=timing, x0=np.concatenate([initial_ptzs[1:].reshape(-1), rays0.reshape(-1)]))
-    if covariance:
-        return landmarks, keyframes, cov
-    return landmarks, keyframes
+    out = (landmarks, keyframes) + ((cov,) if covariance else ()) + ((marg_out,) if leaving is not None else ())
+    return out

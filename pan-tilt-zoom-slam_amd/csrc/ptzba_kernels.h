@@ -397,6 +397,67 @@ constexpr int PRIOR_RED_BLOCKS = 64;
 constexpr int PRIOR_RED_SCRATCH = PRIOR_RED_BLOCKS + 2;
 void launch_prior_cost(const PriorArgs& a, double* out, double mul, int accumulate, double* scratch, hipStream_t st);
 
+// Marginalisation of leaving keyframes and the dense information-form factor it yields (marg_kernels.hip;
+// ptzba_marginal_prior / ptzba_set_marginal_prior)
+constexpr int MARG_MAX_E = 8;    // free leaving frames (A_EE 24 x 24 in LDS)
+constexpr int MARG_MAX_K = 64;   // frames of the marginal (the 192 x 24 panel A_KE in LDS)
+// the handle's dense factor q(x) = offset + eta^T d + 1/2 d^T Lambda d, d = x_F - lin; state selection as PriorArgs
+struct MargArgs {
+  int n;                   // frames (<= MARG_MAX_K)
+  const int32_t* frames;   // [n]
+  const double* lin;       // [3 n]
+  const double* info;      // [3 n x 3 n] symmetric
+  const double* eta;       // [3 n]
+  double offset;
+  const double* x0;
+  const double* x1;
+  const int* sel;
+  int sel_xor;
+};
+// S += Lambda, g_pose += Lambda d + eta, b -= the same, dU += diag Lambda: one thread per written element
+void launch_marg_apply(const MargArgs& a, double* S, int64_t ld, double* b, double* g_pose, double* dU,
+                       const int32_t* frame_pos, const int* skip_if, hipStream_t st);
+// out[0] = q(x) at the selected state (+= with accumulate != 0); one workgroup, fixed summation order
+void launch_marg_cost(const MargArgs& a, double* out, int accumulate, hipStream_t st);
+// w[i] = mask[perm[i]] ? (rec_w ? rec_w[i] : 1) : 0 in the record precision (sorted order); frame_flag[f] = 1 for
+// every frame with a dropped record, lm_flag likewise; cnt[0] += dropped records, cnt[1] += dropped landmarks
+// (flags and counters zeroed by the caller)
+template <typename real>
+void launch_marg_weights(const uint8_t* mask, const int64_t* perm, const void* rec_w, const int32_t* rec_seg,
+                         const int32_t* seg_frame, const int32_t* seg_lm, int64_t n_rec, void* w_out,
+                         int32_t* frame_flag, int32_t* lm_flag, unsigned long long* cnt, hipStream_t st);
+// one absorbed factor of k_marg_eliminate: 1/2 e^T L e (eta == nullptr) or offset + eta^T e + 1/2 e^T L e, e = x[frames]
+// - mean; loc[s] the position of frame slot s in the (K | E) list
+struct MargFactor {
+  int n3;              // 3 G
+  int loc_off;         // first entry of the factor's slots in EliminateArgs::loc / frames
+  const double* L;     // [n3 x n3]
+  const double* mean;  // [n3]
+  const double* eta;   // [n3] or nullptr
+  double offset;
+};
+struct EliminateArgs {
+  int nK, nE;                 // frames of K and free frames of E; rows of (K | E) = 3 (nK + nE)
+  const int32_t* frames;      // [nK + nE] K ascending, then E
+  const int32_t* frame_pos;   // system positions
+  const double* S;            // the built reduced system of the dropped records (lower triangle, pattern tiles)
+  const double* b;            // -b_D
+  int64_t ld;
+  const int32_t* row_tile;    // [3 (nK + nE)] local id of the row's 32-row tile
+  const uint8_t* pat;         // [n_tile x n_tile] 1: the tile pair (larger, smaller system tile) is in the pattern
+  int n_tile;
+  int n_factor;
+  const MargFactor* factors;  // absorbed, in order
+  const int32_t* fac_frames;  // the factors' frames, concatenated
+  const int32_t* fac_loc;     // ... and their positions in (K | E)
+  const double* x;            // the current poses
+  const double* dcost;        // [1] 1/2 sum_D rho
+  double pivot_tol;
+  // out: [Lambda (3 nK)^2 | eta 3 nK | lin 3 nK | offset, min pivot, status (0 ok, 1 + row of E that failed), max diag]
+  double* out;
+};
+void launch_marg_eliminate(const EliminateArgs& a, hipStream_t st);
+
 // camera batch kernels (camera_kernels.hip)
 void launch_ray_to_image(int64_t n, double u, double v, const double* f, const double* cp, const double* ct,
                          const double* th, const double* ph, double* x, double* y, hipStream_t st);

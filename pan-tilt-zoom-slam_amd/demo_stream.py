@@ -9,7 +9,7 @@ The keyframe map is the reference's `Map` (every keyframe adjusted, scene_map.py
 processing, scene_map.py:198-244, with the window the config asks for: 30).  --keyframe-every K adds a
 keyframe every K frames on top of the reference's overlap rule (ptz_slam.py:458), so long windows fill up.
 
-  python demo_stream.py [--frames 300] [--window 30] [--keyframe-every 10] [--json]
+  python demo_stream.py [--frames 300] [--window 30] [--keyframe-every 10] [--marginalize]
 
 Prints one JSON line: end-to-end frames/s, per-frame tracking latency, keyframe BA latency, pose error
 against the ground truth, and the time spent inside the front-end stand-in (synthetic.StreamFrontEnd:
@@ -84,6 +84,9 @@ def main():
     ap.add_argument("--frontend", choices=("gpu", "standin"), default="gpu",
                     help="gpu: rendered 1080p frames through the GPU front-end (SIFT, LK, RANSAC); "
                          "standin: StreamFrontEnd's ground-truth correspondences")
+    ap.add_argument("--marginalize", action="store_true",
+                    help="sliding window: turn the matches of the keyframe that leaves into a prior on the keyframes "
+                         "that stay (Map(marginalize=True)) instead of dropping them")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--gc", choices=("default", "freeze", "scheduled"), default="scheduled",
                     help="freeze: gc.freeze() before the loop -- the ~10^5 objects of the imports (torch, scipy) leave the "
@@ -131,7 +134,7 @@ def main():
             source.image(i)
         t_render = time.perf_counter() - t0
     slam = PtzSlam()
-    slam.keyframe_map = Map("sift", max_ba_frame=a.window or None)
+    slam.keyframe_map = Map("sift", max_ba_frame=a.window or None, marginalize=a.marginalize)
     on_frame = None
     gc_thresholds = gc.get_threshold()
     if a.gc in ("freeze", "scheduled"):
@@ -163,6 +166,7 @@ def main():
                     f"{a.window or 'all'}, keyframe every {a.keyframe_every} frames + overlap rule",
         "frontend": ("GPU SIFT / pyramidal LK / homography RANSAC on rendered frames" if fe is None else
                      "stand-in: ground-truth correspondences (synthetic.StreamFrontEnd)"),
+        "marginalize": bool(a.marginalize and a.window),
         "frames": a.frames, "fps_end_to_end": a.frames / wall, "wall_s": wall, "render_s_outside_loop": t_render,
         "frontend_standin_s": fe_time, "fps_excluding_frontend_standin": a.frames / max(wall - fe_time, 1e-9),
         "tracking_ms": {"mean": 1e3 * float(tt.mean()), "p50": 1e3 * float(np.median(tt)),
@@ -180,6 +184,13 @@ def main():
         "gc": a.gc + (f" (full collections every {a.gc_every} frames, between frames)" if a.gc == "scheduled" else ""),
         "gc_pauses_ms": {str(g): {"count": v[0], "total": v[1], "max": v[2]} for g, v in sorted(gc_stats.items())},
     }
+    # the map's keyframes (the keyframe BA's output; the tracker's poses above do not read them back) against the truth
+    kfs = [k for k in slam.keyframe_map.keyframe_list if 0 <= k.img_index < len(scene.cams)]
+    if kfs:
+        kerr = np.array([[k.pan, k.tilt, k.f] for k in kfs]) - scene.cams[[k.img_index for k in kfs]]
+        out["keyframe_pose_rmse_vs_truth"] = {"pan_deg": float(np.sqrt(np.mean(kerr[:, 0] ** 2))),
+                                              "tilt_deg": float(np.sqrt(np.mean(kerr[:, 1] ** 2))),
+                                              "f_px": float(np.sqrt(np.mean(kerr[:, 2] ** 2))), "keyframes": len(kfs)}
     kt = rec.get("kf_timing", [])[1:]
     if kt:  # where a keyframe's BA call spends its time (bundle_adjustment.LAST_RESULT["timing"], mean ms)
         keys = sorted({k for d in kt for k in d})

@@ -86,6 +86,27 @@ class ptzba_pose_priors(Structure):
 PRIOR_MAX_FRAMES = 8  # frames one prior factor may name (include/ptzba.h)
 
 
+class ptzba_marg_opts(Structure):
+    """include/ptzba.h ptzba_marg_opts."""
+    _fields_ = [("struct_size", c_int32), ("reserved", c_int32), ("pivot_tol", c_double)]
+
+
+class ptzba_marg_stats(Structure):
+    """include/ptzba.h ptzba_marg_stats."""
+    _fields_ = [("struct_size", c_int32), ("marginal_absorbed", c_int32), ("dropped_records", c_int64),
+                ("dropped_landmarks", c_int64), ("n_absorbed", c_int32), ("absorbed_cap", c_int32),
+                ("absorbed", c_void_p), ("min_pivot", c_double), ("device_ms", c_double)]
+
+
+class ptzba_marginal(Structure):
+    """include/ptzba.h ptzba_marginal."""
+    _fields_ = [("struct_size", c_int32), ("n_frame", c_int32), ("frames", c_void_p), ("lin", c_void_p),
+                ("info", c_void_p), ("grad", c_void_p), ("offset", c_double)]
+
+
+MARG_MAX_DROP, MARG_MAX_FRAMES = 8, 64  # include/ptzba.h PTZBA_MARG_MAX_*
+
+
 class ptzba_report(Structure):
     _fields_ = [("cost", c_double), ("initial_cost", c_double), ("time_s", c_double), ("iterations", c_int32),
                 ("nfev", c_int32), ("trials", c_int32), ("status", c_int32)]
@@ -145,6 +166,10 @@ def lib():
         "ptzba_covariance": ([V, POINTER(ptzba_cov_opts), V, V, I32, V, V], I),
         "ptzba_set_pose_priors": ([V, POINTER(ptzba_pose_priors)], I),
         "ptzba_pose_prior_info": ([V, V], I),
+        "ptzba_marginal_prior": ([V, POINTER(ptzba_marg_opts), V, I32, V, I64, I32, V, POINTER(c_int32), V, V, V,
+                                 POINTER(c_double), POINTER(ptzba_marg_stats)], I),
+        "ptzba_set_marginal_prior": ([V, POINTER(ptzba_marginal)], I),
+        "ptzba_marginal_prior_info": ([V, V], I),
         "ptzba_set_setup_front": ([V, I64], I),
         "ptzba_setup_timing": ([V, I32, V, V, V], I),
         "ptzba_solve": ([V, V, V, POINTER(ptzba_lm_opts), POINTER(ptzba_report)], I),
@@ -251,7 +276,8 @@ EXPORTED_SYMBOLS = [
     "ptzba_plan_export", "ptzba_dist_exchanges", "ptzba_dist_groups", "ptzba_exchange_group", "ptzba_dist_plan_summary",
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
-    "ptzba_set_pose_priors", "ptzba_pose_prior_info",
+    "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
+    "ptzba_marginal_prior_info",
 ]
 
 
@@ -794,12 +820,143 @@ def prior_window(n_pose, frame, landmark, factors):
     `frame_win_hi` to pass to set_problem before set_pose_priors (the factor pattern of the reduced system then holds
     the tiles the prior's blocks land in)."""
     win = frame_coupling_window(n_pose, frame, landmark).copy()
-    for frames, _, _ in factors:
+    for fac in factors:
+        frames = fac.frames if isinstance(fac, Marginal) else fac[0]
         fr = np.atleast_1d(np.asarray(frames)).astype(np.int64)
+        if not len(fr):
+            continue
         hi = int(fr.max())
         for f in fr:
             win[f] = max(win[f], hi)
     return win
+
+
+class Marginal:
+    """A dense information-form factor over the poses of `frames` (ptzba_marginal_prior's result):
+
+        q(x) = offset + grad^T d + 1/2 d^T info d,      d = x[frames] - lin
+
+    frames int [n] (distinct), lin float64 [n, 3], info float64 [3 n, 3 n] symmetric PSD, grad float64 [3 n], offset
+    float.  It stays in information form: info may be singular (a marginal over relative observations fixes no
+    gauge), and no method inverts it.  The methods are exact algebra on q and return new objects."""
+
+    def __init__(self, frames, lin, info, grad, offset):
+        self.frames = np.ascontiguousarray(np.atleast_1d(frames), np.int32).reshape(-1)
+        n = len(self.frames)
+        self.lin = np.array(lin, np.float64).reshape(n, 3)
+        self.info = np.array(info, np.float64).reshape(3 * n, 3 * n)
+        self.grad = np.array(grad, np.float64).reshape(3 * n)
+        self.offset = float(offset)
+        if len(set(self.frames.tolist())) != n:
+            raise ValueError("Marginal: a frame is repeated")
+
+    def __repr__(self):
+        return f"Marginal(frames={self.frames.tolist()}, offset={self.offset:.6g})"
+
+    def _poses(self, x):
+        if isinstance(x, dict):
+            return np.array([x[int(f)] for f in self.frames], np.float64).reshape(-1, 3)
+        return np.asarray(x, np.float64).reshape(-1, 3)[self.frames]
+
+    def value(self, x):
+        """q at the poses x: an array [n_pose, 3] indexed by frame, or a dict frame -> pose."""
+        d = (self._poses(x) - self.lin).reshape(-1)
+        return self.offset + float(self.grad @ d) + 0.5 * float(d @ (self.info @ d))
+
+    def relinearise(self, lin):
+        """The same q about another point: grad' = grad + info (lin' - lin), offset' = q(lin')."""
+        lin = np.asarray(lin, np.float64).reshape(self.lin.shape)
+        dl = (lin - self.lin).reshape(-1)
+        Ld = self.info @ dl
+        return Marginal(self.frames, lin, self.info, self.grad + Ld, self.offset + float(self.grad @ dl) + 0.5 * float(dl @ Ld))
+
+    def condition(self, frames, values):
+        """q with the poses of `frames` held at `values` [len(frames), 3] (frames the factor does not name are
+        ignored): grad_r += info_rF d_F, offset += grad_F^T d_F + 1/2 d_F^T info_FF d_F."""
+        frames = np.atleast_1d(np.asarray(frames, np.int64)).reshape(-1)
+        values = np.asarray(values, np.float64).reshape(len(frames), 3)
+        at = {int(f): k for k, f in enumerate(frames)}
+        fix = np.array([int(f) in at for f in self.frames], bool)
+        if not fix.any():
+            return self
+        iF = np.flatnonzero(np.repeat(fix, 3))
+        iR = np.flatnonzero(np.repeat(~fix, 3))
+        dF = (np.array([values[at[int(f)]] for f in self.frames[fix]]) - self.lin[fix]).reshape(-1)
+        return Marginal(self.frames[~fix], self.lin[~fix], self.info[np.ix_(iR, iR)],
+                        self.grad[iR] + self.info[np.ix_(iR, iF)] @ dF,
+                        self.offset + float(self.grad[iF] @ dF) + 0.5 * float(dF @ (self.info[np.ix_(iF, iF)] @ dF)))
+
+    def reindex(self, mapping):
+        """The same factor with frame f renamed mapping[f] (a dict or an index array); frames come out ascending."""
+        new = np.array([mapping[int(f)] for f in self.frames], np.int64)
+        if len(new) and new.min() < 0:
+            raise ValueError("Marginal.reindex: a frame has no image in the mapping")
+        o = np.argsort(new, kind="stable")
+        i3 = (3 * o[:, None] + np.arange(3)[None, :]).reshape(-1)
+        return Marginal(new[o], self.lin[o], self.info[np.ix_(i3, i3)], self.grad[i3], self.offset)
+
+    def expanded(self, frames, lin):
+        """The factor over the superset `frames` (zero rows for the new ones, whose lin comes from `lin`)."""
+        frames = np.asarray(frames, np.int64).reshape(-1)
+        pos = {int(f): k for k, f in enumerate(frames)}
+        idx = np.array([pos[int(f)] for f in self.frames], np.int64)
+        i3 = (3 * idx[:, None] + np.arange(3)[None, :]).reshape(-1)
+        n = len(frames)
+        L = np.zeros((3 * n, 3 * n))
+        g = np.zeros(3 * n)
+        x = np.array(lin, np.float64).reshape(n, 3)
+        L[np.ix_(i3, i3)] = self.info
+        g[i3] = self.grad
+        x[idx] = self.lin
+        return Marginal(frames, x, L, g, self.offset)
+
+
+def merge_marginals(a, b):
+    """a + b as one factor over the union of their frames (ascending), a relinearised to b's point on the frames
+    both name: the summed function is unchanged.  None stands for the zero factor."""
+    if a is None or not len(a.frames):
+        return b if a is None or b is not None and len(b.frames) else a
+    if b is None or not len(b.frames):
+        return a
+    fb = {int(f): k for k, f in enumerate(b.frames)}
+    lin = a.lin.copy()
+    for k, f in enumerate(a.frames):
+        if int(f) in fb:
+            lin[k] = b.lin[fb[int(f)]]
+    a = a.relinearise(lin)
+    union = np.array(sorted(set(a.frames.tolist()) | set(b.frames.tolist())), np.int64)
+    zero = np.zeros((len(union), 3))
+    ea, eb = a.expanded(union, zero), b.expanded(union, zero)
+    named_b = np.array([int(f) in fb for f in union], bool)
+    return Marginal(union, np.where(named_b[:, None], eb.lin, ea.lin), ea.info + eb.info, ea.grad + eb.grad,
+                    ea.offset + eb.offset)
+
+
+def drop_mask(frame, drop_frames):
+    """The record mask (uint8, one per record) of the pair form -- records 2m and 2m + 1 are the two observations of
+    match m -- that marks both records of every match with a record in one of `drop_frames`."""
+    frame = np.asarray(frame).reshape(-1)
+    if len(frame) % 2:
+        raise ValueError("drop_mask: the pair form has an even number of records")
+    hit = np.isin(frame, np.atleast_1d(np.asarray(drop_frames)))
+    return np.repeat(hit[0::2] | hit[1::2], 2).astype(np.uint8)
+
+
+_pair_drop_mask = drop_mask  # (BAHandle.marginal_prior has a parameter of the function's name)
+
+
+def check_marginal(m):
+    """ValueError unless m.info is finite, symmetric and positive semi-definite (check_pose_priors' rule: no
+    eigenvalue below -1e-12 max|info|)."""
+    if not (np.isfinite(m.info).all() and np.isfinite(m.grad).all() and np.isfinite(m.lin).all() and np.isfinite(m.offset)):
+        raise ValueError("marginal prior: non-finite value")
+    if not len(m.frames):
+        return
+    amax = float(np.abs(m.info).max())
+    if np.abs(m.info - m.info.T).max() > 1e-12 * amax:
+        raise ValueError("marginal prior: info is not symmetric")
+    if amax > 0 and np.linalg.eigvalsh(0.5 * (m.info + m.info.T)).min() < -1e-12 * amax:
+        raise ValueError("marginal prior: info is not positive semi-definite")
 
 
 def plan_summary(frame_win_hi, n_fixed=1, ordering=None):
@@ -1061,6 +1218,8 @@ class BAHandle:
         _check(lib().ptzba_set_problem(self.h, int(n_pose), int(n_landmark), n, _ptr(frame), _ptr(landmark), _ptr(xy),
                                        _ptr(w), float(u), float(v), ctypes.byref(opts)), "ptzba_set_problem")
         self.n_pose, self.n_landmark, self.n_obs = int(n_pose), int(n_landmark), n
+        self.n_fixed = int(n_fixed)
+        self._frame = frame  # (marginal_prior's default mask)
         self.precision = precision
         self.loss = int(loss)
 
@@ -1264,6 +1423,60 @@ class BAHandle:
         out = np.zeros(4)
         _check(lib().ptzba_pose_prior_info(self.h, _ptr(out)), "ptzba_pose_prior_info")
         return int(out[0]), int(out[1]), int(out[2]), float(out[3])
+
+    def marginal_prior(self, drop_frames, drop_mask=None, pivot_tol=0.0, _struct_size=None):
+        """ptzba_marginal_prior at the current state (a between-solves call): the Marginal that stands for the records
+        of `drop_mask` (default: ptzba.drop_mask of the problem's frames, the pair form) and for every factor naming a
+        leaving frame, with the leaving frames `drop_frames` eliminated.  Returns (Marginal, stats dict: dropped_records,
+        dropped_landmarks, absorbed (pose-prior factor indices), marginal_absorbed, min_pivot, device_ms)."""
+        E = np.ascontiguousarray(np.atleast_1d(drop_frames), np.int32).reshape(-1)
+        mask = _pair_drop_mask(self._frame, E) if drop_mask is None else \
+            np.ascontiguousarray(np.asarray(drop_mask).reshape(-1) != 0, np.uint8)
+        cap = MARG_MAX_FRAMES
+        frames = np.zeros(cap, np.int32)
+        lin, info, grad = np.zeros(3 * cap), np.zeros(9 * cap * cap), np.zeros(3 * cap)
+        n_out, offset = c_int32(0), c_double(0.0)
+        absorbed = np.zeros(max(self.pose_prior_info()[0], 1), np.int32)
+        stats = ptzba_marg_stats(ctypes.sizeof(ptzba_marg_stats), 0, 0, 0, 0, len(absorbed), _ptr(absorbed).value, 0.0, 0.0)
+        opts = ptzba_marg_opts(ctypes.sizeof(ptzba_marg_opts) if _struct_size is None else int(_struct_size), 0,
+                               float(pivot_tol))
+        _check(lib().ptzba_marginal_prior(self.h, ctypes.byref(opts), _ptr(E), len(E), _ptr(mask), len(mask), cap,
+                                          _ptr(frames), ctypes.byref(n_out), _ptr(lin), _ptr(info), _ptr(grad),
+                                          ctypes.byref(offset), ctypes.byref(stats)), "ptzba_marginal_prior")
+        n = n_out.value
+        m = Marginal(frames[:n], lin[:3 * n], info[:9 * n * n], grad[:3 * n], offset.value)
+        return m, dict(dropped_records=int(stats.dropped_records), dropped_landmarks=int(stats.dropped_landmarks),
+                       absorbed=absorbed[:stats.n_absorbed].tolist(), marginal_absorbed=bool(stats.marginal_absorbed),
+                       min_pivot=float(stats.min_pivot), device_ms=float(stats.device_ms))
+
+    def set_marginal_prior(self, m, _struct_size=None, _raw=False):
+        """The handle's one dense information-form factor (ptzba_set_marginal_prior); None or an empty Marginal clears
+        it.  Frames below n_fixed are conditioned at the handle's current state; info must be positive semi-definite
+        (check_marginal).  A pair outside the handle's coupling window is refused (PtzbaError): pass
+        prior_window(..., [m]) as set_problem's frame_win_hi."""
+        if m is None:
+            return self.clear_marginal_prior()
+        if not _raw:
+            fixed = m.frames[m.frames < self.n_fixed]
+            if len(fixed):
+                m = m.condition(fixed, self.get_state()[0][fixed])
+            check_marginal(m)
+        if not len(m.frames):
+            return self.clear_marginal_prior()
+        fr = np.ascontiguousarray(m.frames, np.int32)
+        lin, info, grad = (np.ascontiguousarray(a, np.float64) for a in (m.lin, m.info, m.grad))
+        c = ptzba_marginal(ctypes.sizeof(ptzba_marginal) if _struct_size is None else int(_struct_size), len(fr),
+                           _ptr(fr).value, _ptr(lin).value, _ptr(info).value, _ptr(grad).value, float(m.offset))
+        _check(lib().ptzba_set_marginal_prior(self.h, ctypes.byref(c)), "ptzba_set_marginal_prior")
+
+    def clear_marginal_prior(self):
+        _check(lib().ptzba_set_marginal_prior(self.h, None), "ptzba_set_marginal_prior")
+
+    def marginal_prior_info(self):
+        """(frames, rows, offset, q at the current state)."""
+        out = np.zeros(4)
+        _check(lib().ptzba_marginal_prior_info(self.h, _ptr(out)), "ptzba_marginal_prior_info")
+        return int(out[0]), int(out[1]), float(out[2]), float(out[3])
 
     def build_reduced(self, lam):
         _check(lib().ptzba_build_reduced(self.h, float(lam)), "ptzba_build_reduced")
@@ -1714,7 +1927,8 @@ def _cov_kwargs(covariance):
 
 
 def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, weight=None, precision=FP64,
-          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, pose_priors=None, **lm_kw):
+          loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, pose_priors=None,
+          marginal_prior=None, marginalize=None, **lm_kw):
     """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
     BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
     (pose_cov, ray_cov, info) at the solution.  keep_handle=True (default): one
@@ -1722,11 +1936,29 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
     destroying a handle -- stream, pinned records, device buffers -- cost ~6 ms per call); set_problem replaces
     its problem and release_solve_handles() frees it.  keep_handle=False: a private handle, closed on return.
     The shared handle is used under a lock: concurrent callers on one device run one at a time.
-    pose_priors: a prior factor list (BAHandle.set_pose_priors); the coupling window is raised for it (prior_window)."""
+    pose_priors: a prior factor list (BAHandle.set_pose_priors); the coupling window is raised for it (prior_window).
+    marginal_prior: a Marginal (BAHandle.set_marginal_prior; frame 0, the gauge, is conditioned at init_ptz[0]).
+    marginalize: a list of leaving frames -- the last element of the result is then {"marginal": Marginal, "stats":
+    dict}, BAHandle.marginal_prior(marginalize) at the solution."""
     win = None
     if pose_priors:
         pose_priors = check_pose_priors(pose_priors, n_pose)
-        win = prior_window(n_pose, frame, landmark, pose_priors)
+    if marginal_prior is not None:
+        if len(marginal_prior.frames) and (marginal_prior.frames.min() < 0 or marginal_prior.frames.max() >= n_pose):
+            raise ValueError("marginal_prior: frame out of range")
+        marginal_prior = marginal_prior.condition([0], np.asarray(init_ptz, np.float64).reshape(-1, 3)[:1])
+        if not len(marginal_prior.frames):
+            marginal_prior = None
+    if pose_priors or marginal_prior is not None:
+        win = prior_window(n_pose, frame, landmark, list(pose_priors or []) + ([marginal_prior] if marginal_prior is not None else []))
+
+    def finish(h, out):
+        if covariance:
+            out = out + (h.covariance(**_cov_kwargs(covariance)),)
+        if marginalize is not None:
+            m, stats = h.marginal_prior(marginalize)
+            out = out + (dict(marginal=m, stats=stats),)
+        return out
     if not keep_handle:
         h = BAHandle(device)
         try:
@@ -1735,11 +1967,11 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
             if pose_priors:
                 h.set_pose_priors(pose_priors)
             h.set_state(init_ptz, init_rays)
+            if marginal_prior is not None:
+                h.set_marginal_prior(marginal_prior)
             res = LMSolver(h, **lm_kw).run()
             ptz, rays = h.get_state()
-            if covariance:
-                return ptz, rays, res, h.covariance(**_cov_kwargs(covariance))
-            return ptz, rays, res
+            return finish(h, (ptz, rays, res))
         finally:
             h.close()
     with _solve_lock:
@@ -1756,6 +1988,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                 h.set_pose_priors(pose_priors)
             t1 = time.perf_counter()
             h.set_state(init_ptz, init_rays)
+            if marginal_prior is not None:
+                h.set_marginal_prior(marginal_prior)
             t2 = time.perf_counter()
             res = LMSolver(h, **lm_kw).run()
             t3 = time.perf_counter()
@@ -1765,9 +1999,7 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                 LAST_SOLVE_TIMING["setup_" + k.replace("+", "_").replace(" ", "_") + "_s"] = v * 1e-3
             LAST_SOLVE_TIMING.update(set_problem_s=t1 - t0, lm_s=time.perf_counter() - t1, lm_set_state_s=t2 - t1,
                                      lm_run_s=t3 - t2, lm_get_state_s=time.perf_counter() - t3)
-            if covariance:
-                return ptz, rays, res, h.covariance(**_cov_kwargs(covariance))
-            return ptz, rays, res
+            return finish(h, (ptz, rays, res))
         except Exception:
             _solve_handles.pop(device, None)
             h.close()

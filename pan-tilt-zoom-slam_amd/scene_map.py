@@ -23,12 +23,52 @@ from key_frame import KeyFrame
 from util import overlap_pan_angle
 
 
+class MarginalCarry:
+    """The information a sliding window keeps of the keyframes that left it: one ptzba.Marginal keyed
+    by image index.  Per BA call: `before(window image indices)` merges the marginal computed for a keyframe that has
+    now left, conditions the stored factor on every keyframe outside the window at that keyframe's kept pose, and
+    returns the factor to pass as bundle_adjustment's marginal_prior; `after(...)` records the poses of the call and
+    the marginal of the window's first keyframe, which the next keyframe pushes out."""
+
+    def __init__(self):
+        self.stored = None
+        self.pending = None  # (image index, Marginal): merged once that keyframe has left the window
+        self.poses = {}      # image index -> (pan, tilt, f) as last adjusted
+
+    def note(self, keyframes):
+        for k in keyframes:
+            self.poses[k.img_index] = (k.pan, k.tilt, k.f)
+
+    def before(self, window):
+        import ptzba
+        window = set(window)
+        if self.pending is not None:
+            idx, m = self.pending
+            if idx not in window and m is not None:
+                self.stored = ptzba.merge_marginals(self.stored, m)
+            self.pending = None
+        if self.stored is not None:
+            gone = [int(f) for f in self.stored.frames if int(f) not in window]
+            if gone:
+                self.stored = self.stored.condition(gone, np.array([self.poses[f] for f in gone], np.float64))
+            if not len(self.stored.frames):
+                self.stored = None
+        return self.stored
+
+    def after(self, keyframes, leaving, result):
+        self.note(keyframes)
+        if result is not None:
+            self.pending = (leaving, result["marginal"])
+
+
 class Map:
     """max_ba_frame: None (the reference: every keyframe is adjusted) or N: only the last N keyframes are
     adjusted, older ones stay as they are (RandomForestMap's window rule, scene_map.py:198-244; the
-    streaming config's 30-keyframe window)."""
+    streaming config's 30-keyframe window).  marginalize=True (with a window): the matches of the keyframe a full
+    window is about to lose are turned into a prior on the keyframes that stay (MarginalCarry) instead of being thrown
+    away."""
 
-    def __init__(self, feature_method, cache_correspondences=True, max_ba_frame=None):
+    def __init__(self, feature_method, cache_correspondences=True, max_ba_frame=None, marginalize=False):
         assert feature_method in ("sift", "orb", "latch")
         self.global_ray = np.ndarray([0, 2])
         self.keyframe_list = []
@@ -37,6 +77,7 @@ class Map:
         self.last_ba_time = None
         self.max_ba_frame = max_ba_frame
         self.correspondences = CorrespondenceCache() if cache_correspondences else None
+        self.marginal_carry = MarginalCarry() if marginalize and max_ba_frame else None
 
     def add_first_keyframe(self, keyframe, verbose=False):
         assert isinstance(keyframe, KeyFrame)
@@ -77,11 +118,21 @@ class Map:
         images = [k.img for k in self.keyframe_list]
         image_indices = [k.img_index for k in self.keyframe_list]
         initial_ptzs = np.array([[k.pan, k.tilt, k.f] for k in self.keyframe_list], dtype=np.float64).reshape(n, 3)
+        carry, leaving = self.marginal_carry, None
+        if carry is not None:
+            carry.note(kept + self.keyframe_list[:-1])
+            prior_kw["marginal_prior"] = carry.before(image_indices)
+            if n == self.max_ba_frame:
+                leaving = image_indices[0]
+                prior_kw["marginalize"] = [leaving]
         start = time.time()
-        landmarks, keyframes = bundle_adjustment(images, image_indices, self.feature_method, initial_ptzs, ref.center,
-                                                 ref.base_rotation, ref.u, ref.v, save_path, verbose,
-                                                 correspondences=self.correspondences, **self.ba_options, **prior_kw)
+        out = bundle_adjustment(images, image_indices, self.feature_method, initial_ptzs, ref.center,
+                                ref.base_rotation, ref.u, ref.v, save_path, verbose,
+                                correspondences=self.correspondences, **self.ba_options, **prior_kw)
+        landmarks, keyframes = out[:2]
         end = time.time()
+        if carry is not None:
+            carry.after(keyframes, leaving, out[-1] if leaving is not None else None)
         self.keyframe_list.pop()
         self.global_ray = landmarks
         self.keyframe_list = list(kept)
