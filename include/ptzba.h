@@ -168,6 +168,11 @@ PTZBA_EXPORT int ptzba_k1_info(ptzba_handle h, int64_t* info4);
  * list, then how many items have [4] at most 16 landmarks (one batch), [5] nl % 32 in 1..16 (odd batch count),
  * [6] nl % 32 in 17..31 (even count, ragged last batch), [7] nl % 32 == 0 */
 PTZBA_EXPORT int ptzba_k2_info(ptzba_handle h, int* info8);
+/* host only: the reduced-system kernel's tiles (block of 32 free frames x chunk of 64 partner frames; a tile's landmark
+ * list is cut into splits = work items, whose partials the tile reduction sums eight at a time): [0] tiles, [1] / [2]
+ * fewest / most splits of a tile, [3] tiles with at least 9 splits (the eight-in-flight loop and its remainder),
+ * [4] the highest chunk index, [5] tiles whose partner range f1b + 64 (chunk + 1) passes n_pose; [6], [7] zero */
+PTZBA_EXPORT int ptzba_k2_tile_info(ptzba_handle h, int32_t* out8);
 /* host phase times of the last ptzba_set_problem (sort, segments, K2 structure, plan, uploads ...): names[k] (static
  * strings) and ms[k] for k < min(cap, *n_out); *n_out = the number of phases recorded */
 PTZBA_EXPORT int ptzba_setup_timing(ptzba_handle h, int32_t cap, const char** names, double* ms, int32_t* n_out);
@@ -400,7 +405,12 @@ PTZBA_EXPORT int ptzba_read_scalars(ptzba_handle h, double* out /*PTZBA_NSCALARS
 PTZBA_EXPORT int ptzba_accept(ptzba_handle h, int accept);
 /* Device pointers of the exchange regions (fp64): reduced system (ld*ld + 3*ld doubles, ld = the padded
  * system dimension: the lower triangle of S row-major in the system order, then b, g_pose and diag U)
- * and the additive partial scalars (PTZBA_NSCALARS). */
+ * and the additive partial scalars (PTZBA_NSCALARS).  After ptzba_build_reduced the region is raw whatever the
+ * environment says -- S without pose damping, rows from n_aug on zero -- and ptzba_solve_reduced adds lambda D_pose,
+ * the row b^T at n_aug and the padding diagonal; a build of the device-driven LM (ptzba_lm_build) on one GPU without
+ * priors writes those itself (lambda D_pose on the pose diagonal, b^T in row n_aug, 1 on padding rows, 1e300 at
+ * (n_aug, n_aug)) unless PTZBA_NO_FUSED_PREP is set or sys_ptr has been asked for before (a caller that holds the
+ * pointer may sum the system between build and solve), which leave it raw as well. */
 PTZBA_EXPORT int ptzba_exchange(ptzba_handle h, void** sys_ptr, int64_t* sys_count, void** scal_ptr);
 /* Packed exchange for sharded solves: a contiguous device buffer (fp64, *count doubles) holding only
  * the tiles of the reduced system the Schur kernel can write, then b | g_pose | dU.  Sequence per

@@ -68,6 +68,7 @@ struct ptzba_ctx {
   int n_s2_items = 0, n_s2_groups = 0;
   int k2_pipe = 1;     // fp32 K2 kernel: 1 producer / consumer waves (waves 0-3 stage), 2 (even waves stage), 0 k_schur_mf
   int k2_info[8] = {};  // ptzba_k2_info
+  int k2_tile_info[8] = {};  // ptzba_k2_tile_info
   int64_t n_slot = 0;  // dense landmark x frame slots (W table rows)
   // device: state
   DBuf ptz, rays, ptz_trial, rays_trial, D_pose, D_ray;
@@ -1804,6 +1805,21 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
         ++ki[m == 0 ? 7 : (m <= 16 ? 5 : 6)];
       }
     }
+    // which reduce shapes the tiles run (ptzba_k2_tile_info): splits per tile against the reduce's 8 partials in
+    // flight, the farthest partner chunk, partner ranges that pass the last frame (the clamped reads)
+    {
+      int* ti = h->k2_tile_info;
+      for (int k = 0; k < 8; ++k) ti[k] = 0;
+      ti[0] = h->n_s2_groups;
+      for (size_t g = 0; g < s2_groups.size(); g += 4) {
+        const int ns = s2_groups[g + 3] - s2_groups[g + 2];
+        ti[1] = g == 0 ? ns : std::min(ti[1], ns);
+        ti[2] = std::max(ti[2], ns);
+        if (ns >= 9) ++ti[3];
+        ti[4] = std::max(ti[4], s2_groups[g + 1]);
+        if (s2_groups[g] + WAVE * (s2_groups[g + 1] + 1) > n_pose) ++ti[5];
+      }
+    }
     // PTZBA_K2_PIPE=0: the block-synchronous k_schur_mf (kept for one round: A/B and the bitwise parity test);
     // =even: the even waves stage instead of waves 0-3
     h->k2_pipe = getenv_is("PTZBA_K2_PIPE", "0") ? 0 : (getenv_is("PTZBA_K2_PIPE", "even") ? 2 : 1);
@@ -2129,6 +2145,13 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
 int ptzba_k2_info(ptzba_handle h, int* out) {
   if (!h || !h->have_problem) return fail("no problem set");
   for (int k = 0; k < 8; ++k) out[k] = h->k2_info[k];
+  return 0;
+}
+
+int ptzba_k2_tile_info(ptzba_handle h, int32_t* out) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!out) return fail("bad arguments");
+  for (int k = 0; k < 8; ++k) out[k] = h->k2_tile_info[k];
   return 0;
 }
 

@@ -527,7 +527,11 @@ def test_reduced_system_matrix_core_k2_matches_fp64(gpu_available, config, loss)
     """K2 of the fp32 path runs on the matrix cores (k_schur_mf: fp16 hi/lo operand splits with power-of-
     two landmark scaling); the fp64 path keeps the VALU kernel.  At the same linearisation point the two reduced camera systems (S | b | g_pose
     | diag U, the exchange region) agree to the fp32 record precision, element by element against each row's
-    scale."""
+    scale.  Both builds share the tile lists, landmark windows, splits, frame positions and the tile reduction, so an
+    error in any of those is common-mode here: tests/test_gpu_k2_reference.py holds both kernels against a dense fp64
+    reference that knows none of them, on small problems crafted for every shape of the builder and the reduce.  What
+    this test still adds are the full configurations 2 and 3 (hundreds of items, lists and split counts as the solver
+    meets them)."""
     import torch
     import bench
     import ptzba

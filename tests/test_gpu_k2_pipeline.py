@@ -10,33 +10,12 @@ import numpy as np
 import pytest
 
 import k1_cases as kc
+from k2_cases import tiny as _tiny
 
 pytestmark = pytest.mark.gpu
 
 SETTINGS = ("0", None, "even")  # PTZBA_K2_PIPE: k_schur_mf, the default (waves 0-3 stage), the even waves stage
 _cache = {}
-
-
-def _tiny():
-    """12 landmarks over 100 poses (3 seen by every frame, 9 by 12 consecutive frames): every K2 list has at most 16
-    landmarks, and the all-frame landmarks reach partner chunk 1."""
-    from oracle import ptz_oracle as orc
-    rng = np.random.default_rng(11)
-    n_pose, u, v = 100, 640.0, 360.0
-    frames = [np.arange(n_pose)] * 3 + [np.arange(s, s + 12) for s in range(0, 99, 11)][:9]
-    landmark = np.concatenate([np.full(len(f), l) for l, f in enumerate(frames)]).astype(np.int32)
-    frame = np.concatenate(frames).astype(np.int32)
-    n_lm = len(frames)
-    ptz = np.stack([np.linspace(48.0, 56.0, n_pose), -10.0 + rng.normal(0, 0.2, n_pose),
-                    3000.0 + rng.normal(0, 40.0, n_pose)], -1)
-    rays = np.stack([rng.uniform(50.0, 54.0, n_lm), rng.uniform(-12.0, -8.0, n_lm)], -1)
-    px, py = orc.from_ray_to_image(u, v, ptz[frame, 2], ptz[frame, 0], ptz[frame, 1], rays[landmark, 0], rays[landmark, 1])
-    xy = np.stack([px, py], -1) + rng.normal(0, 0.5, (len(frame), 2))
-    xy[::7] += 6.0  # both Huber branches
-    ptz0 = ptz + rng.normal(0, 1.0, (n_pose, 3)) * np.array([0.015, 0.01, 5.0])
-    ptz0[0] = ptz[0]
-    return dict(n_pose=n_pose, n_landmark=n_lm, frame=frame, landmark=landmark, xy=xy, u=u, v=v, ptz=ptz0,
-                rays=rays + rng.normal(0, 0.01, (n_lm, 2)))
 
 
 def _problem(name):
