@@ -394,6 +394,40 @@ typedef struct {
 PTZBA_EXPORT int ptzba_set_marginal_prior(ptzba_handle h, const ptzba_marginal* m);
 /* out4: [0] frames, [1] rows, [2] offset, [3] q(x) at the handle's current state (0 without a marginal) */
 PTZBA_EXPORT int ptzba_marginal_prior_info(ptzba_handle h, double* out4);
+/* Gaussian ray priors (ptzba_version 0.6).  Prior k names one landmark l_k, a mean mu_k (theta, phi in
+ * degrees) and a symmetric positive semi-definite 2 x 2 information matrix Lambda_k (1/deg^2); the objective gains
+ *     1/2 sum_k e_k^T Lambda_k e_k,     e_k = ray_{l_k} - mu_k
+ * (plain differences, no wrap; neither the loss nor the Huber curvature factor applies to the prior terms).  Several
+ * priors may name one landmark; their terms add in list order.  The prior is block-diagonal in the landmark part:
+ * V_l += sum Lambda_k, g_l += sum Lambda_k e_k and the landmark's cost share gains the prior's cost, on every solve path
+ * (ptzba_linearize / step / accept, ptzba_lm_*, ptzba_solve, ptzba_solve_resident).  Everything that reads V_l and g_l
+ * follows: the reduced system, the ray back-substitution and predicted reduction, the gradient maximum, the Marquardt
+ * memory of the rays (diag Lambda counts as the whitened prior rows' column norms would), every reported cost
+ * (ptzba_read_scalars [0] / [1], ptzba_lm_record, ptzba_report) and ptzba_covariance (blocks of scale * (J^T J + P_pose
+ * + P_ray)^-1).  ptzba_covariance's scale_mode 2 counts every ray prior as two residual rows: the numerator gains
+ * sum_k e_k^T Lambda_k e_k, the denominator 2 n_prior (a rank-deficient Lambda_k is over-counted, as for pose priors).
+ * ptzba_marginal_prior is not affected: a ray prior belongs to the landmark that stays, not to the independent copy
+ * eliminated with the dropped records; the call leaves the handle as ptzba_linearize does, ray priors included.
+ *
+ * The arrays are copied.  NULL or n_prior == 0 clears the priors.  Valid after ptzba_set_problem, between solves;
+ * cleared by ptzba_set_problem; persistent over ptzba_set_state / ptzba_save_state / ptzba_restore_state; independent
+ * of the pose-prior list and of the marginal factor (all three may be set together).
+ * Refused with a message, the handle left as it was: a struct_size this library does not know; a landmark out of
+ * range; a landmark without records (prior-only landmarks are not supported); a non-finite value; a negative diagonal
+ * entry; L01^2 > L00 L11 (1 + 1e-12) (not positive semi-definite); a pending LM trial; a sharded handle, or one with a
+ * communicator or hook attached or a caller-run exchange protocol in use.  While ray priors are set,
+ * ptzba_attach_comm and ptzba_set_exchange_hook are refused. */
+typedef struct {
+  int32_t struct_size;      /* sizeof(ptzba_ray_priors) */
+  int32_t n_prior;
+  const int32_t* landmark;  /* [n_prior] */
+  const double* mean;       /* [n_prior][2]  theta, phi (deg) */
+  const double* info;       /* [n_prior][3]  L00, L01, L11 */
+} ptzba_ray_priors;
+PTZBA_EXPORT int ptzba_set_ray_priors(ptzba_handle h, const ptzba_ray_priors* priors);
+/* out4: [0] priors, [1] distinct landmarks under a prior, [2] prior rows (2 n_prior), [3] the ray-prior cost
+ * 1/2 sum_k e_k^T Lambda_k e_k at the handle's current state (0 without ray priors) */
+PTZBA_EXPORT int ptzba_ray_prior_info(ptzba_handle h, double* out4);
 /* Which front builds the record arrays in the following ptzba_set_problem calls of this handle (round 6): the device
  * front (one rocPRIM radix sort + segment / record kernels) from min_records records on, the host's counting sorts
  * below.  0: always the device, INT64_MAX: never, -1: the default (64K records since round 6, 4M before: configs 3 and 4

@@ -125,7 +125,7 @@ class _KeyframeLists:
 def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, center, rotation, u, v, save_path,
                       verbose=False, precision="fp64", loss="linear", f_scale=1.0, ftol=1e-4, xtol=1e-8,
                       max_iter=100, device=0, correspondences=None, *, covariance=False, pose_priors=None,
-                      marginal_prior=None, marginalize=None):
+                      marginal_prior=None, marginalize=None, ray_priors=None):
     """bundle_adjustment.py:109-251 on the MI355X path.  Returns (landmarks [M,2], keyframes).
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
@@ -141,6 +141,15 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     marginalize (keyword only): a list of image indices that are about to leave the window -- the returned tuple gains
     a last element {"marginal": ptzba.Marginal keyed by image index (None without records), "stats": dict}, the
     marginal of those images' matches at the returned solution (ptzba.BAHandle.marginal_prior).
+    ray_priors (keyword only; off: the call and its outputs are unchanged): Gaussian ray priors [(image index,
+    keypoint index, mean, info), ...] -- landmark ids are assigned inside the call, so a prior names its landmark by a
+    keypoint: a row of that image's detection (KeyFrame.keypoint_index; stable across calls that share a
+    CorrespondenceCache).  Each key resolves through the call's matches to the landmark the keypoint belongs to and adds
+    1/2 e^T info e, e = that ray (theta, phi) minus mean, to the objective (ptzba.check_ray_priors' form; several keys
+    on one landmark are several priors).  An image index that is not part of the call raises ValueError; a keypoint
+    that no match of the call uses is skipped and its key listed in LAST_RESULT["ray_priors_skipped"];
+    LAST_RESULT["ray_priors_used"] is the number of priors set.  ptzba.ray_priors_from_result builds the list from a
+    covariance=True result.
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
@@ -175,6 +184,21 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         if any(k not in where for k in keys):
             raise ValueError("marginalize: image index not among image_indices")
         leaving = [where[k] for k in keys]
+    ray_keys = None
+    if ray_priors:
+        ray_keys = []
+        for n, pr in enumerate(ray_priors):
+            try:
+                key, kp, mean, info = pr
+            except (TypeError, ValueError):
+                raise ValueError(f"ray prior {n}: expected (image index, keypoint index, mean, info)")
+            if key not in where:
+                raise ValueError(f"ray prior {n}: image index not among image_indices")
+            kp = np.asarray(kp)
+            if kp.ndim != 0 or not np.issubdtype(kp.dtype, np.integer) or int(kp) < 0:
+                raise ValueError(f"ray prior {n}: keypoint index must be one non-negative integer")
+            ray_keys.append((where[key], int(kp), key))
+        ptzba.check_ray_priors([(0, pr[2], pr[3]) for pr in ray_priors])  # means and infos, before any image work
     timing = {}
     t_start = time.time()
 
@@ -216,6 +240,20 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
                                     xy[rec, 1], device=device)
         rays0[lids, 0] = th
         rays0[lids, 1] = ph
+    rpriors, rp_skipped = None, []
+    if ray_keys is not None:
+        # (frame, keypoint) -> landmark through the call's matches, the first match in loop order winning
+        lm_of = {}
+        for f, k, l in zip(np.concatenate([g.m_i, g.m_j]).tolist(), np.concatenate([g.k1, g.k2]).tolist(),
+                           np.concatenate([g.lm, g.lm]).tolist()):
+            lm_of.setdefault((f, k), l)
+        rpriors = []
+        for (f, k, key), pr in zip(ray_keys, ray_priors):
+            l = lm_of.get((f, k))
+            if l is None:
+                rp_skipped.append((key, k))
+            else:
+                rpriors.append((int(l), pr[2], pr[3]))
     timing["records"] = time.time() - t1
 
     # step 3: optimisation on the GPU (replaces bundle_adjustment.py:200-202)
@@ -231,7 +269,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
                           covariance=True if covariance else None, pose_priors=priors, marginal_prior=marg,
-                          marginalize=leaving)
+                          marginalize=leaving, ray_priors=rpriors or None)
         all_poses, landmarks, res = out[:3]
         if leaving is not None:
             marg_out = dict(marginal=out[-1]["marginal"].reindex(dict(enumerate(image_indices))), stats=out[-1]["stats"])
@@ -261,5 +299,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     LAST_RESULT.clear()
     LAST_RESULT.update(result=res, n_residual=n_residual, n_landmark=n_landmark, time=timing["solve"],
                        timing=timing, x0=np.concatenate([initial_ptzs[1:].reshape(-1), rays0.reshape(-1)]))
+    if ray_keys is not None:
+        LAST_RESULT.update(ray_priors_used=len(rpriors) if len(frame) else 0, ray_priors_skipped=rp_skipped)
     out = (landmarks, keyframes) + ((cov,) if covariance else ()) + ((marg_out,) if leaving is not None else ())
     return out

@@ -203,6 +203,13 @@ struct ptzba_ctx {
     DBuf red;   // [PRIOR_RED_SCRATCH] k_prior_cost's partials and counter (zeroed when allocated)
     std::vector<int32_t> h_begin, h_frames;  // host copies of f_begin / f_frames (ptzba_marginal_prior's absorption)
   } pri;
+  // Gaussian ray priors (ptzba_set_ray_priors; prior_kernels.hip RayPriorArgs): a CSR over the distinct landmarks.  They
+  // change lm_out's rows (V, g, cost) after K1 and nothing else, so the fused prepare stays on with them alone.
+  struct RayPriors {
+    int n_prior = 0, n_lm = 0;
+    DBuf lm, begin, mean, info;
+    DBuf cost;  // [1] ptzba_ray_prior_info's read-back
+  } rp;
   std::vector<int32_t> win_host, pos_host;  // the problem's coupling window and system positions (prior validation)
   // marginalisation (ptzba_marginal_prior / ptzba_set_marginal_prior; marg_kernels.hip)
   struct Marg {
@@ -224,6 +231,7 @@ struct ptzba_ctx {
   std::vector<int32_t> zt_host;     // host copy of ztiles (the factor pattern; ptzba_marginal_prior's gather)
   bool has_priors() const { return pri.n_factor > 0; }
   bool has_marg() const { return mg.n > 0; }
+  bool has_ray_priors() const { return rp.n_prior > 0; }
   bool fused_prep() const {
     return !no_fused_prep && !dist_mode && !has_exchange() && !ext_exchange && f1_covered && !has_priors() && !has_marg();
   }
@@ -301,9 +309,10 @@ const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.3: ptzba_covariance / ptzba_cov_opts (sized by its struct_size field); ptzba_lm_opts as in 0.2.
 // 0.4: ptzba_set_pose_priors / ptzba_pose_priors (sized by struct_size) / ptzba_pose_prior_info.
 // 0.5: ptzba_marginal_prior / ptzba_set_marginal_prior / ptzba_marginal_prior_info (structs sized by struct_size).
+// 0.6: ptzba_set_ray_priors / ptzba_ray_priors (sized by struct_size) / ptzba_ray_prior_info.
 const char* ptzba_version(void) {
-  return "ptzba 0.5 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
-         "ptzba_marginal_prior)";
+  return "ptzba 0.6 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
+         "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors)";
 }
 
 ptzba_handle ptzba_new(int device) {
@@ -1506,6 +1515,7 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   h->pri.n_factor = 0;  // a new problem starts without pose priors
   h->mg.n = 0;          // ... without a marginal factor, and without ptzba_marginal_prior's work buffers
   h->mg.release_work();
+  h->rp.n_prior = 0;    // ... and without ray priors
   h->w_override = nullptr;
   h->trial_open = false;
   h->ptz_saved.release();
@@ -2182,8 +2192,11 @@ static void tables(ptzba_ctx* h, const double* ptz, const double* rays, const in
 // run_if != nullptr: a conditional re-linearisation of the current point (device-driven LM, after the curvature
 // switch): the launch exits at once unless *run_if; not timed as a K1 launch (the roofline averages real ones)
 // hc_dev: device-driven LM, the huber curvature weight from device memory (LMDev::hc / hc_trial); nullptr: h->hcurv
+// trial_state: the tables of this linearisation were made from the trial state (k_trial's output), not the current
+// one (the ray priors form e from the same rays)
+static RayPriorArgs ray_prior_args(const ptzba_ctx* h, const int* sel, int flip);  // (below, next to prior_args)
 static void linearize_into(ptzba_ctx* h, int slot, const int* sel = nullptr, int sel_xor = 0,
-                           const int* run_if = nullptr, const double* hc_dev = nullptr) {
+                           const int* run_if = nullptr, const double* hc_dev = nullptr, bool trial_state = false) {
   LinArgs a;
   a.lm_work = h->lm_order.as<int4>();
   a.n_work = h->n_work;
@@ -2228,6 +2241,11 @@ static void linearize_into(ptzba_ctx* h, int slot, const int* sel = nullptr, int
   else
     launch_linearize<double>(a, h->loss, h->st, e0, e1);
   if (!run_if) tm_end(h, TM_K1);
+  // ray priors: V_l, g_l and the landmark's cost share of the rows K1 has just written -- the same slot selector and
+  // gate as K1, e from the rays its tables were made from (outside the timed K1 group).  Not under w_override:
+  // ptzba_marginal_prior linearises the dropped records alone, the priors stay with the landmarks that remain
+  if (h->has_ray_priors() && !h->w_override)
+    launch_ray_prior_apply(ray_prior_args(h, sel, trial_state ? 1 : 0), a.lm_out, a.lm_out1, sel, sel_xor, run_if, h->st);
 }
 
 int ptzba_solver_info(ptzba_handle h, int64_t* info8) {
@@ -2425,6 +2443,31 @@ static PriorArgs prior_args(const ptzba_ctx* h, const int* sel, int flip) {
   a.p_diag = p.p_diag.as<double>();
   const double* cur = h->ptz.as<double>();
   const double* oth = h->ptz_trial.as<double>();
+  if (sel) {
+    a.x0 = cur;
+    a.x1 = oth;
+    a.sel = sel;
+    a.sel_xor = h->state_base ^ flip;
+  } else {
+    a.x0 = flip ? oth : cur;
+    a.x1 = nullptr;
+    a.sel = nullptr;
+    a.sel_xor = 0;
+  }
+  return a;
+}
+
+// the handle's ray priors over the state pair (rays, rays_trial), selected as prior_args selects (ptz, ptz_trial)
+static RayPriorArgs ray_prior_args(const ptzba_ctx* h, const int* sel, int flip) {
+  const auto& p = h->rp;
+  RayPriorArgs a;
+  a.n_lm = p.n_lm;
+  a.lm = p.lm.as<int32_t>();
+  a.begin = p.begin.as<int32_t>();
+  a.mean = p.mean.as<double>();
+  a.info = p.info.as<double>();
+  const double* cur = h->rays.as<double>();
+  const double* oth = h->rays_trial.as<double>();
   if (sel) {
     a.x0 = cur;
     a.x1 = oth;
@@ -2660,7 +2703,7 @@ static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* se
                          h->st, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, &cd);
     }
   }
-  linearize_into(h, nx, sel, 1, nullptr, hc_dev);
+  linearize_into(h, nx, sel, 1, nullptr, hc_dev, true);
   // scal[1] (trial cost) and scal[2..5] are overwritten below, loc[0..3] by the trial kernel: no memsets
   if (sel && !h->has_exchange() && !h->ext_exchange && !h->scal_exported && !h->dist_mode) {
     // launched by ptzba_lm_decide with the decision fused into it (nothing runs between the two calls)
@@ -2980,6 +3023,7 @@ int ptzba_set_exchange_hook(ptzba_handle h, ptzba_exchange_fn fn, void* ctx) {
   if (!h) return fail("null handle");
   if (fn && h->has_marg()) return fail("ptzba_set_exchange_hook: the handle has a marginal prior set (single rank only)");
   if (fn && h->has_priors()) return fail("ptzba_set_exchange_hook: the handle has pose priors set (single rank only)");
+  if (fn && h->has_ray_priors()) return fail("ptzba_set_exchange_hook: the handle has ray priors set (single rank only)");
   h->hook = fn;
   h->hook_ctx = ctx;
   return 0;
@@ -2989,6 +3033,7 @@ int ptzba_attach_comm(ptzba_handle h, ptzba_comm comm) {
   if (!h) return fail("null handle");
   if (comm && h->has_marg()) return fail("ptzba_attach_comm: the handle has a marginal prior set (single rank only)");
   if (comm && h->has_priors()) return fail("ptzba_attach_comm: the handle has pose priors set (single rank only)");
+  if (comm && h->has_ray_priors()) return fail("ptzba_attach_comm: the handle has ray priors set (single rank only)");
   h->drop_groups();
   h->comm = comm;
   return 0;  // the group communicator is split lazily by the first exchange (collective, every rank reaches it)
@@ -3785,6 +3830,97 @@ int ptzba_pose_prior_info(ptzba_handle h, double* out4) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Gaussian ray priors (include/ptzba.h ptzba_set_ray_priors; prior_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// Everything is validated on the host before the handle is touched.  The priors are sorted by landmark (stable, so a
+// landmark's priors keep their list order) into the CSR k_ray_prior_apply walks: one thread per distinct landmark.
+int ptzba_set_ray_priors(ptzba_handle h, const ptzba_ray_priors* pr) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (pr && pr->struct_size != (int32_t)sizeof(ptzba_ray_priors))
+    return fail("ptzba_set_ray_priors: unknown struct_size %d of ptzba_ray_priors (this library knows %d)",
+                (int)pr->struct_size, (int)sizeof(ptzba_ray_priors));
+  if (h->trial_open)
+    return fail("ptzba_set_ray_priors: an LM trial is pending (accept or reject it first; the call runs between solves)");
+  HIPCHK(hipSetDevice(h->device));
+  if (!pr || pr->n_prior == 0) {
+    HIPCHK(hipStreamSynchronize(h->st));  // queued work may still read the set's arrays
+    h->rp.n_prior = 0;
+    h->rp.n_lm = 0;
+    return 0;
+  }
+  if (h->dist_mode || h->dist_world > 1 || h->has_exchange() || h->ext_exchange || h->scal_exported)
+    return fail("ptzba_set_ray_priors: single rank only (the handle is sharded, has a communicator / hook attached "
+                "or runs a caller-side exchange)");
+  const int n = pr->n_prior;
+  if (n < 0 || !pr->landmark || !pr->mean || !pr->info)
+    return fail("ptzba_set_ray_priors: bad arguments (n_prior %d, null array)", n);
+  std::vector<int32_t> seg((size_t)h->n_lm + 1);
+  HIPCHK(hipMemcpyAsync(seg.data(), h->lm_seg_begin.p, seg.size() * 4, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  for (int k = 0; k < n; ++k) {
+    const int l = pr->landmark[k];
+    if (l < 0 || l >= h->n_lm) return fail("ptzba_set_ray_priors: prior %d names landmark %d, out of range [0, %d)", k, l, h->n_lm);
+    if (seg[l + 1] == seg[l])
+      return fail("ptzba_set_ray_priors: prior %d names landmark %d, which has no records (prior-only landmarks are "
+                  "not supported)", k, l);
+    const double* m = pr->mean + 2 * (size_t)k;
+    const double* L = pr->info + 3 * (size_t)k;
+    if (!std::isfinite(m[0]) || !std::isfinite(m[1])) return fail("ptzba_set_ray_priors: prior %d: non-finite mean", k);
+    if (!std::isfinite(L[0]) || !std::isfinite(L[1]) || !std::isfinite(L[2]))
+      return fail("ptzba_set_ray_priors: prior %d: non-finite information entry", k);
+    if (L[0] < 0.0 || L[2] < 0.0)
+      return fail("ptzba_set_ray_priors: prior %d: negative diagonal entry %g of the information matrix", k,
+                  L[0] < 0.0 ? L[0] : L[2]);
+    if (L[1] * L[1] > L[0] * L[2] * (1.0 + 1e-12))
+      return fail("ptzba_set_ray_priors: prior %d: information matrix not positive semi-definite (L01^2 = %g > L00 L11 = %g)",
+                  k, L[1] * L[1], L[0] * L[2]);
+  }
+  std::vector<int32_t> order(n);
+  for (int k = 0; k < n; ++k) order[k] = k;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return pr->landmark[a] < pr->landmark[b]; });
+  std::vector<int32_t> lm, begin;
+  std::vector<double> mean(2 * (size_t)n), info(3 * (size_t)n);
+  for (int q = 0; q < n; ++q) {
+    const int k = order[q], l = pr->landmark[k];
+    if (lm.empty() || lm.back() != l) {
+      lm.push_back(l);
+      begin.push_back(q);
+    }
+    for (int e = 0; e < 2; ++e) mean[2 * (size_t)q + e] = pr->mean[2 * (size_t)k + e];
+    for (int e = 0; e < 3; ++e) info[3 * (size_t)q + e] = pr->info[3 * (size_t)k + e];
+  }
+  begin.push_back(n);
+  // queued work may still read the previous set's arrays
+  HIPCHK(hipStreamSynchronize(h->st));
+  auto& p = h->rp;
+  p.n_prior = 0;
+  p.n_lm = 0;
+  if (upload(p.lm, lm, h->st) || upload(p.begin, begin, h->st) || upload(p.mean, mean, h->st) || upload(p.info, info, h->st))
+    return -1;
+  p.n_lm = (int)lm.size();
+  p.n_prior = n;
+  return 0;
+}
+
+int ptzba_ray_prior_info(ptzba_handle h, double* out4) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!out4) return fail("ptzba_ray_prior_info: null output");
+  const auto& p = h->rp;
+  out4[0] = p.n_prior;
+  out4[1] = p.n_prior ? p.n_lm : 0;
+  out4[2] = 2.0 * p.n_prior;
+  out4[3] = 0.0;
+  if (!h->has_ray_priors()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->rp.cost.p && h->rp.cost.alloc(8)) return -1;
+  launch_ray_prior_cost(ray_prior_args(h, nullptr, 0), h->rp.cost.as<double>(), 1.0, 0, h->st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out4 + 3, h->rp.cost.p, 8, hipMemcpyDeviceToHost, h->st));
+  HIPCHK(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // marginalisation of leaving keyframes (include/ptzba.h ptzba_marginal_prior; marg_kernels.hip)
 // ------------------------------------------------------------------------------------------------
 static bool single_rank(const ptzba_ctx* h) {
@@ -4225,9 +4361,11 @@ int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* o, double* pose_cov, 
   auto& c = h->cov;
   const int n_free = 3 * (h->n_pose - h->n_fixed) + 2 * c.n_active;
   // pose priors: every prior row counts as a residual (rank-deficient factors over-count, include/ptzba.h)
-  const double dof = 2.0 * (double)h->n_rec + (h->has_priors() ? (double)h->pri.n_row : 0.0) - (double)n_free;
+  // ray priors likewise: two rows each
+  const int64_t n_prior_rows = (h->has_priors() ? (int64_t)h->pri.n_row : 0) + (h->has_ray_priors() ? 2 * (int64_t)h->rp.n_prior : 0);
+  const double dof = 2.0 * (double)h->n_rec + (double)n_prior_rows - (double)n_free;
   if (opt.scale_mode == 2 && !(dof > 0)) return fail("ptzba_covariance: residual scale needs more residuals (%lld) than "
-                                                     "free parameters (%d)", (long long)(2 * h->n_rec + (h->has_priors() ? h->pri.n_row : 0)), n_free);
+                                                     "free parameters (%d)", (long long)(2 * h->n_rec + n_prior_rows), n_free);
   const int n_ray_blocks = (int)((n_sel + CHOL_NB / 2 - 1) / (CHOL_NB / 2));
   const int n_pose_blocks = pose_cov ? c.n_pose_blocks : 0;
   const int n_groups = std::min(c.max_groups, n_pose_blocks + n_ray_blocks);
@@ -4269,6 +4407,7 @@ int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* o, double* pose_cov, 
   }
   // ... + sum_k e_k^T Lambda_k e_k, twice the prior cost
   if (opt.scale_mode == 2 && h->has_priors()) launch_prior_cost(prior_args(h, nullptr, 0), resid, 2.0, 1, h->pri.red.as<double>(), h->st);
+  if (opt.scale_mode == 2 && h->has_ray_priors()) launch_ray_prior_cost(ray_prior_args(h, nullptr, 0), resid, 2.0, 1, h->st);
   if (build_impl(h, 0.0, nullptr) || factor_impl(h, nullptr, nullptr)) return -1;
   HIPCHK(hipMemcpyAsync(h->D_pose.p, dsave, h->D_pose.bytes, hipMemcpyDeviceToDevice, h->st));
   HIPCHK(hipMemcpyAsync(h->D_ray.p, dsave + h->D_pose.bytes / 8, h->D_ray.bytes, hipMemcpyDeviceToDevice, h->st));

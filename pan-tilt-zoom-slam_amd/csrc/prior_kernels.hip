@@ -7,6 +7,7 @@
 // S, b, g_pose and dU of a build and adds the prior's terms in place; k_prior_cost gives the prior's share of the
 // cost at the current or the trial state.  Both form e in fp64 from the state itself (never from the fp32 tables).
 // Every written element has one owning thread and the sums run in a fixed order: results are bitwise repeatable.
+// The Gaussian ray priors (ptzba_set_ray_priors) are at the end of the file.
 #include <algorithm>
 
 #include "ptzba_common.h"
@@ -103,6 +104,81 @@ __global__ __launch_bounds__(256) void k_prior_cost(PriorArgs a, double* __restr
     out[0] = accumulate ? out[0] + c : c;
     __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gaussian ray priors (include/ptzba.h ptzba_set_ray_priors).  A prior on a ray is block-diagonal in
+// the landmark part: V_l += sum Lambda_k, g_l += sum Lambda_k e_k, the landmark's cost share += 1/2 sum e^T Lambda e,
+// and nothing else changes -- every later kernel reads V_l, g_l and the cost from the landmark's lm_out row.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const double* ray_prior_state(const RayPriorArgs& a) {
+  return (a.sel && (((*a.sel) ^ a.sel_xor) & 1)) ? a.x1 : a.x0;
+}
+
+// One thread per distinct prior landmark: the sums of its priors in list order, added to the row K1 wrote for the
+// landmark (the launch follows K1 on the stream).  A row has one owning thread: plain loads and stores, no atomics.
+__global__ __launch_bounds__(256) void k_ray_prior_apply(RayPriorArgs a, double* __restrict__ lm_out,
+                                                         double* __restrict__ lm_out1,
+                                                         const int* __restrict__ slot_sel, int slot_xor,
+                                                         const int* __restrict__ run_if) {
+  if (run_if && !*run_if) return;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.n_lm) return;
+  const bool alt = slot_sel && ((*slot_sel ^ slot_xor) & 1);
+  const double* __restrict__ x = ray_prior_state(a);
+  const int l = a.lm[t];
+  const double th = x[2 * (int64_t)l], ph = x[2 * (int64_t)l + 1];
+  double v00 = 0.0, v01 = 0.0, v11 = 0.0, g0 = 0.0, g1 = 0.0, c = 0.0;
+  for (int k = a.begin[t]; k < a.begin[t + 1]; ++k) {
+    const double l00 = a.info[3 * (int64_t)k], l01 = a.info[3 * (int64_t)k + 1], l11 = a.info[3 * (int64_t)k + 2];
+    const double e0 = th - a.mean[2 * (int64_t)k], e1 = ph - a.mean[2 * (int64_t)k + 1];
+    const double r0 = l00 * e0 + l01 * e1, r1 = l01 * e0 + l11 * e1;
+    v00 += l00; v01 += l01; v11 += l11;
+    g0 += r0; g1 += r1;
+    c += e0 * r0 + e1 * r1;
+  }
+  double* o = (alt ? lm_out1 : lm_out) + (int64_t)l * 8;
+  o[0] += v00; o[1] += v01; o[2] += v11; o[3] += g0; o[4] += g1; o[5] += 0.5 * c;
+}
+
+// 1/2 sum e^T Lambda e: thread t sums the landmarks t, t + 256, ... (each landmark's priors in list order), the waves
+// and then the workgroup add in a fixed order; the grid is one workgroup, so the result is the same on every launch
+__global__ __launch_bounds__(256) void k_ray_prior_cost(RayPriorArgs a, double* __restrict__ out, double mul,
+                                                        int accumulate) {
+  __shared__ double red[256 / WAVE];
+  const double* __restrict__ x = ray_prior_state(a);
+  double acc = 0.0;
+  for (int t = threadIdx.x; t < a.n_lm; t += blockDim.x) {
+    const int l = a.lm[t];
+    const double th = x[2 * (int64_t)l], ph = x[2 * (int64_t)l + 1];
+    double c = 0.0;
+    for (int k = a.begin[t]; k < a.begin[t + 1]; ++k) {
+      const double l00 = a.info[3 * (int64_t)k], l01 = a.info[3 * (int64_t)k + 1], l11 = a.info[3 * (int64_t)k + 2];
+      const double e0 = th - a.mean[2 * (int64_t)k], e1 = ph - a.mean[2 * (int64_t)k + 1];
+      c += e0 * (l00 * e0 + l01 * e1) + e1 * (l01 * e0 + l11 * e1);
+    }
+    acc += c;
+  }
+  acc = wave_sum(acc);
+  if (lane_id() == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int w = 0; w < 256 / WAVE; ++w) s += red[w];
+    const double c = mul * (0.5 * s);
+    out[0] = accumulate ? out[0] + c : c;
+  }
+}
+
+void launch_ray_prior_apply(const RayPriorArgs& a, double* lm_out, double* lm_out1, const int* slot_sel, int slot_xor,
+                            const int* run_if, hipStream_t st) {
+  if (a.n_lm <= 0) return;
+  hipLaunchKernelGGL(k_ray_prior_apply, dim3((unsigned)((a.n_lm + 255) / 256)), dim3(256), 0, st, a, lm_out, lm_out1,
+                     slot_sel, slot_xor, run_if);
+}
+
+void launch_ray_prior_cost(const RayPriorArgs& a, double* out, double mul, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(k_ray_prior_cost, dim3(1), dim3(256), 0, st, a, out, mul, accumulate);
 }
 
 void launch_prior_apply(const PriorArgs& a, double* S, double* b, double* g_pose, double* dU, const int32_t* frame_pos,

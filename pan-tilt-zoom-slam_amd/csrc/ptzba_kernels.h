@@ -397,6 +397,29 @@ constexpr int PRIOR_RED_BLOCKS = 64;
 constexpr int PRIOR_RED_SCRATCH = PRIOR_RED_BLOCKS + 2;
 void launch_prior_cost(const PriorArgs& a, double* out, double mul, int accumulate, double* scratch, hipStream_t st);
 
+// Gaussian ray priors (prior_kernels.hip; ptzba_set_ray_priors): prior k names one landmark, a mean
+// (theta, phi) and a symmetric 2 x 2 information matrix; cost += 1/2 sum_k e_k^T Lambda_k e_k, e_k = ray_{l_k} - mean_k.
+// The host sorts the priors by landmark (stable: list order inside a landmark) into a CSR over the distinct landmarks.
+struct RayPriorArgs {
+  int n_lm;                 // distinct landmarks under a prior
+  const int32_t* lm;        // [n_lm] ascending
+  const int32_t* begin;     // [n_lm + 1] CSR of the priors naming the landmark, list order
+  const double* mean;       // [n_prior][2] in CSR order
+  const double* info;       // [n_prior][3] L00, L01, L11 in CSR order
+  // the rays e is formed from: x0, or x1 when sel != nullptr and ((*sel) ^ sel_xor) is odd (PriorArgs' rule)
+  const double* x0;
+  const double* x1;
+  const int* sel;
+  int sel_xor;
+};
+// lm_out[l][0..5] += (L00, L01, L11, (L e)_0, (L e)_1, 1/2 e^T L e) summed over the landmark's priors in list order, into
+// the rows K1 has just written: slot ((*slot_sel) ^ slot_xor) odd -> lm_out1, else lm_out (LinArgs' rule; slot_sel ==
+// nullptr: lm_out).  One thread per distinct landmark, no atomics.  run_if as K1's launch.
+void launch_ray_prior_apply(const RayPriorArgs& a, double* lm_out, double* lm_out1, const int* slot_sel, int slot_xor,
+                            const int* run_if, hipStream_t st);
+// out[0] = mul * 1/2 sum_k e^T Lambda e (+= with accumulate != 0); one workgroup, fixed summation order
+void launch_ray_prior_cost(const RayPriorArgs& a, double* out, double mul, int accumulate, hipStream_t st);
+
 // Marginalisation of leaving keyframes and the dense information-form factor it yields (marg_kernels.hip;
 // ptzba_marginal_prior / ptzba_set_marginal_prior)
 constexpr int MARG_MAX_E = 8;    // free leaving frames (A_EE 24 x 24 in LDS)

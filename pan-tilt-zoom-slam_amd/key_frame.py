@@ -36,6 +36,7 @@ class KeyFrame:
         self._pts = np.ndarray(0)
         self._des = np.ndarray(0)
         self._lmi = []
+        self._kpi = np.zeros(0, np.int64)
         self.pan, self.tilt, self.f = pan, tilt, f
         self.center = center
         self.base_rotation = rotation
@@ -59,6 +60,7 @@ class KeyFrame:
         else:
             idx, glo = prov.lists(pos)
             self._lmi = glo.astype(np.int32)
+            self._kpi = np.asarray(idx, np.int64).copy()
         if isinstance(kps, np.ndarray):
             self._pts = np.asarray(kps)[idx]
         else:
@@ -76,6 +78,15 @@ class KeyFrame:
         if self._lazy is not None:
             self._materialise()
         self._lmi = value
+
+    @property
+    def keypoint_index(self):
+        """The row of each feature in its image's detection (the keypoint array bundle_adjustment saw), parallel to
+        landmark_index: with the image index, a key for a landmark that is stable across calls sharing a
+        CorrespondenceCache (bundle_adjustment's ray_priors).  Empty for a keyframe built by hand."""
+        if self._lazy is not None:
+            self._materialise()
+        return self._kpi
 
     @property
     def feature_pts(self):

@@ -86,6 +86,12 @@ class ptzba_pose_priors(Structure):
 PRIOR_MAX_FRAMES = 8  # frames one prior factor may name (include/ptzba.h)
 
 
+class ptzba_ray_priors(Structure):
+    """include/ptzba.h ptzba_ray_priors; struct_size = ctypes.sizeof(ptzba_ray_priors)."""
+    _fields_ = [("struct_size", c_int32), ("n_prior", c_int32), ("landmark", c_void_p), ("mean", c_void_p),
+                ("info", c_void_p)]
+
+
 class ptzba_marg_opts(Structure):
     """include/ptzba.h ptzba_marg_opts."""
     _fields_ = [("struct_size", c_int32), ("reserved", c_int32), ("pivot_tol", c_double)]
@@ -167,6 +173,8 @@ def lib():
         "ptzba_covariance": ([V, POINTER(ptzba_cov_opts), V, V, I32, V, V], I),
         "ptzba_set_pose_priors": ([V, POINTER(ptzba_pose_priors)], I),
         "ptzba_pose_prior_info": ([V, V], I),
+        "ptzba_set_ray_priors": ([V, POINTER(ptzba_ray_priors)], I),
+        "ptzba_ray_prior_info": ([V, V], I),
         "ptzba_marginal_prior": ([V, POINTER(ptzba_marg_opts), V, I32, V, I64, I32, V, POINTER(c_int32), V, V, V,
                                  POINTER(c_double), POINTER(ptzba_marg_stats)], I),
         "ptzba_set_marginal_prior": ([V, POINTER(ptzba_marginal)], I),
@@ -278,7 +286,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
     "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
-    "ptzba_marginal_prior_info",
+    "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info",
 ]
 
 
@@ -830,6 +838,100 @@ def prior_window(n_pose, frame, landmark, factors):
         for f in fr:
             win[f] = max(win[f], hi)
     return win
+
+
+def check_ray_priors(priors, n_landmark=None):
+    """Validate a ray prior list [(landmark, mean[2], info[2, 2]), ...] on the host and return the flat arrays
+    (landmark int32 [n], mean float64 [n, 2], info float64 [n, 3] = L00, L01, L11): prior k puts the Gaussian prior
+    1/2 e^T info e, e = ray[landmark] - mean (theta, phi in degrees, plain differences), on one landmark's ray.  Several
+    priors may name the same landmark.  info is symmetrised when its asymmetry is within 1e-12 max|info|.  ValueError for
+    a bad shape, a landmark out of range, a non-finite value, asymmetry beyond that bound or an eigenvalue below
+    -1e-12 max|info|."""
+    priors = list(priors)
+    n = len(priors)
+    lm = np.zeros(n, np.int32)
+    mean = np.zeros((n, 2), np.float64)
+    info3 = np.zeros((n, 3), np.float64)
+    for k, pr in enumerate(priors):
+        try:
+            l, m, L = pr
+        except (TypeError, ValueError):
+            raise ValueError(f"ray prior {k}: expected (landmark, mean, info)")
+        l = np.asarray(l)
+        if l.ndim != 0 or not np.issubdtype(l.dtype, np.integer):
+            raise ValueError(f"ray prior {k}: landmark must be one integer")
+        if int(l) < 0 or (n_landmark is not None and int(l) >= n_landmark):
+            raise ValueError(f"ray prior {k}: landmark out of range")
+        try:
+            m = np.asarray(m, np.float64)
+            L = np.asarray(L, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"ray prior {k}: mean and info must be numeric")
+        if m.size != 2 or L.shape != (2, 2):
+            raise ValueError(f"ray prior {k}: mean needs 2 values and info shape (2, 2); got {m.shape} and {L.shape}")
+        if not (np.isfinite(m).all() and np.isfinite(L).all()):
+            raise ValueError(f"ray prior {k}: non-finite value")
+        amax = float(np.abs(L).max())
+        if abs(L[0, 1] - L[1, 0]) > 1e-12 * amax:
+            raise ValueError(f"ray prior {k}: info is not symmetric")
+        L = 0.5 * (L + L.T)
+        if amax > 0 and np.linalg.eigvalsh(L).min() < -1e-12 * amax:
+            raise ValueError(f"ray prior {k}: info is not positive semi-definite")
+        lm[k] = int(l)
+        mean[k] = m.reshape(2)
+        info3[k] = (L[0, 0], L[0, 1], L[1, 1])
+    return lm, mean, info3
+
+
+def ray_priors_from_covariance(landmarks, rays, ray_cov, inflate=1.0, min_eig=0.0):
+    """The ray prior list [(landmark, mean, info), ...] that hands a covariance() result back in: for landmark
+    landmarks[i] the mean rays[i] (theta, phi) and info = inv(inflate * ray_cov[i]).  Zero blocks (landmarks without
+    records) and blocks whose smaller eigenvalue is <= min_eig are skipped.
+
+    Warning: a posterior block already holds what the observations of its solve say about the ray.  Using it as a prior
+    in a problem that still contains those observations counts them twice and makes the result over-confident
+    (DESIGN.md 4.8).  It is meant for problems whose records are new: later keyframes against a known map, or a window
+    from which the observations that taught the ray have left."""
+    landmarks = np.atleast_1d(np.asarray(landmarks)).astype(np.int64)
+    rays = np.asarray(rays, np.float64).reshape(-1, 2)
+    ray_cov = np.asarray(ray_cov, np.float64).reshape(-1, 2, 2)
+    if not (len(landmarks) == len(rays) == len(ray_cov)):
+        raise ValueError("ray_priors_from_covariance: landmarks, rays and ray_cov differ in length")
+    if not (inflate > 0 and np.isfinite(inflate)):
+        raise ValueError("ray_priors_from_covariance: inflate must be positive and finite")
+    out = []
+    for l, r, C in zip(landmarks, rays, ray_cov):
+        if not C.any() or not np.isfinite(C).all():
+            continue
+        C = 0.5 * (C + C.T)
+        if np.linalg.eigvalsh(C).min() <= max(float(min_eig), 0.0):
+            continue
+        out.append((int(l), r.copy(), np.linalg.inv(float(inflate) * C)))
+    return out
+
+
+def ray_priors_from_result(keyframes, landmarks, ray_cov, inflate=1.0):
+    """The keyed ray prior list [(image_index, keypoint_index, mean, info), ...] for bundle_adjustment(ray_priors=...)
+    from a bundle_adjustment(..., covariance=True) result: `keyframes` the returned key frames, `landmarks` the returned
+    rays [n, 2] and `ray_cov` LAST_RESULT["ray_cov"] [n, 2, 2].  Every landmark with a non-zero block appears once, keyed
+    through the first keyframe (in list order) that holds it: (that keyframe's img_index, the keypoint's row in the
+    image's detection), mean = its ray, info = inv(inflate * block).
+
+    Warning: as ray_priors_from_covariance -- a posterior re-used as a prior in a problem that still holds the same
+    observations counts them twice."""
+    landmarks = np.asarray(landmarks, np.float64).reshape(-1, 2)
+    ray_cov = np.asarray(ray_cov, np.float64).reshape(-1, 2, 2)
+    key = {}
+    for kf in keyframes:
+        li = np.asarray(kf.landmark_index).reshape(-1)
+        ki = np.asarray(kf.keypoint_index).reshape(-1)
+        if len(li) != len(ki):
+            raise ValueError("ray_priors_from_result: a keyframe carries no keypoint_index (built by hand?)")
+        for l, k in zip(li.tolist(), ki.tolist()):
+            key.setdefault(int(l), (int(kf.img_index), int(k)))
+    ids = sorted(key)
+    by_lm = dict((l, (m, L)) for l, m, L in ray_priors_from_covariance(ids, landmarks[ids], ray_cov[ids], inflate))
+    return [(key[l][0], key[l][1], by_lm[l][0], by_lm[l][1]) for l in ids if l in by_lm]
 
 
 class Marginal:
@@ -1433,6 +1535,26 @@ class BAHandle:
         _check(lib().ptzba_pose_prior_info(self.h, _ptr(out)), "ptzba_pose_prior_info")
         return int(out[0]), int(out[1]), int(out[2]), float(out[3])
 
+    def set_ray_priors(self, priors):
+        """Gaussian ray priors (ptzba_set_ray_priors): priors = [(landmark, mean[2], info[2, 2]), ...], see
+        check_ray_priors.  Copied; replaces the previous set; an empty list clears.  A landmark without records is
+        refused (PtzbaError)."""
+        lm, mean, info = check_ray_priors(priors, self.n_landmark)
+        if not len(lm):
+            return self.clear_ray_priors()
+        pr = ptzba_ray_priors(ctypes.sizeof(ptzba_ray_priors), len(lm), _ptr(lm).value, _ptr(mean).value,
+                              _ptr(info).value)
+        _check(lib().ptzba_set_ray_priors(self.h, ctypes.byref(pr)), "ptzba_set_ray_priors")
+
+    def clear_ray_priors(self):
+        _check(lib().ptzba_set_ray_priors(self.h, None), "ptzba_set_ray_priors")
+
+    def ray_prior_info(self):
+        """(priors, distinct landmarks under a prior, prior rows 2 n, ray-prior cost at the current state)."""
+        out = np.zeros(4)
+        _check(lib().ptzba_ray_prior_info(self.h, _ptr(out)), "ptzba_ray_prior_info")
+        return int(out[0]), int(out[1]), int(out[2]), float(out[3])
+
     def marginal_prior(self, drop_frames, drop_mask=None, pivot_tol=0.0, _struct_size=None):
         """ptzba_marginal_prior at the current state (a between-solves call): the Marginal that stands for the records
         of `drop_mask` (default: ptzba.drop_mask of the problem's frames, the pair form) and for every factor naming a
@@ -1937,7 +2059,7 @@ def _cov_kwargs(covariance):
 
 def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, weight=None, precision=FP64,
           loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, pose_priors=None,
-          marginal_prior=None, marginalize=None, **lm_kw):
+          marginal_prior=None, marginalize=None, ray_priors=None, **lm_kw):
     """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
     BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
     (pose_cov, ray_cov, info) at the solution.  keep_handle=True (default): one
@@ -1948,8 +2070,12 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
     pose_priors: a prior factor list (BAHandle.set_pose_priors); the coupling window is raised for it (prior_window).
     marginal_prior: a Marginal (BAHandle.set_marginal_prior; frame 0, the gauge, is conditioned at init_ptz[0]).
     marginalize: a list of leaving frames -- the last element of the result is then {"marginal": Marginal, "stats":
-    dict}, BAHandle.marginal_prior(marginalize) at the solution."""
+    dict}, BAHandle.marginal_prior(marginalize) at the solution.
+    ray_priors: a ray prior list [(landmark, mean, info), ...] (BAHandle.set_ray_priors), set after set_problem."""
     win = None
+    if ray_priors is not None:
+        ray_priors = list(ray_priors)
+        check_ray_priors(ray_priors, n_landmark)
     if pose_priors:
         pose_priors = check_pose_priors(pose_priors, n_pose)
     if marginal_prior is not None:
@@ -1975,6 +2101,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                           f_scale=f_scale, frame_win_hi=win)
             if pose_priors:
                 h.set_pose_priors(pose_priors)
+            if ray_priors:
+                h.set_ray_priors(ray_priors)
             h.set_state(init_ptz, init_rays)
             if marginal_prior is not None:
                 h.set_marginal_prior(marginal_prior)
@@ -1995,6 +2123,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                           f_scale=f_scale, frame_win_hi=win)
             if pose_priors:
                 h.set_pose_priors(pose_priors)
+            if ray_priors:
+                h.set_ray_priors(ray_priors)
             t1 = time.perf_counter()
             h.set_state(init_ptz, init_rays)
             if marginal_prior is not None:
