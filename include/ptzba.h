@@ -778,6 +778,11 @@ PTZBA_EXPORT int ptzekf_update(ptzekf_handle h, double u, double v, const double
                                int32_t height, int32_t width, double observe_var, double* velocity_out,
                                int32_t* n_matched_out);
 
+/* host only, read-only (round 8): the reduced-system kernel's tiles themselves, as the tile reduction walks them:
+ * out4[4 k ..] = {first frame of the block, chunk, first item, end item} of tile k < min(cap, *n_out) (end - first =
+ * the tile's splits; see ptzba_k2_tile_info); *n_out = the number of tiles.  out4 may be NULL with cap 0. */
+PTZBA_EXPORT int ptzba_schur_groups(ptzba_handle h, int32_t cap, int32_t* out4, int32_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

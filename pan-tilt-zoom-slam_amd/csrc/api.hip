@@ -62,6 +62,7 @@ struct ptzba_ctx {
   // device: structure
   DBuf rec_xy, rec_seg, rec_w, perm, rec_key;
   DBuf seg_frame, seg_lm, seg_rec_begin, lm_seg_begin, lm_order;
+  DBuf seg_row;  // [n_seg] system row of the segment's frame, -1: fixed (k_trial; launch_seg_row in set_problem)
   DBuf frame_seg_begin, frame_seg_list, frame_win_hi;
   DBuf s2_items, s2_groups, s2_lm, lm_meta;  // K2 work items / tiles / lists, slot ranges
   DBuf s2_part, part_diag;                                    // K2 split partials (blocks, diagonal terms)
@@ -69,6 +70,7 @@ struct ptzba_ctx {
   int k2_pipe = 1;     // fp32 K2 kernel: 1 producer / consumer waves (waves 0-3 stage), 2 (even waves stage), 0 k_schur_mf
   int k2_info[8] = {};  // ptzba_k2_info
   int k2_tile_info[8] = {};  // ptzba_k2_tile_info
+  std::vector<int32_t> s2_groups_host;  // ptzba_schur_groups: the tiles' {f1b, chunk, first item, end item}
   int64_t n_slot = 0;  // dense landmark x frame slots (W table rows)
   // device: state
   DBuf ptz, rays, ptz_trial, rays_trial, D_pose, D_ray;
@@ -2021,6 +2023,7 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
       return -1;
     h->perm_host = std::move(order);
   }
+  h->s2_groups_host = s2_groups;
   if (upload_st(h, h->lm_seg_begin, lm_seg_begin) ||
       upload_st(h, h->lm_order, lm_work) || upload_st(h, h->frame_seg_begin, frame_seg_begin) ||
       upload_st(h, h->frame_seg_list, frame_seg_list) || upload_st(h, h->frame_win_hi, frame_win_hi) ||
@@ -2118,6 +2121,11 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
     return -1;
   if (flush_stage(h)) return -1;
   h->stage_batch = false;
+  // k_trial's per-segment system rows: seg_frame (uploaded, or made by the device front) and frame_pos have landed
+  if (h->seg_row.alloc(4 * (size_t)std::max<int64_t>(h->n_seg, 1))) return -1;
+  launch_seg_row(h->seg_frame.as<int32_t>(), h->frame_pos.as<int32_t>(), h->n_seg, h->n_fixed, h->seg_row.as<int32_t>(),
+                 h->st);
+  HIPCHK(hipGetLastError());
   st_mark("upload+alloc");
   if (!h->scal_host) HIPCHK(hipHostMalloc((void**)&h->scal_host, 24 * sizeof(double), hipHostMallocDefault));
   if (!h->scal_pack.p && h->scal_pack.alloc(24 * sizeof(double))) return -1;
@@ -2155,6 +2163,14 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
 int ptzba_k2_info(ptzba_handle h, int* out) {
   if (!h || !h->have_problem) return fail("no problem set");
   for (int k = 0; k < 8; ++k) out[k] = h->k2_info[k];
+  return 0;
+}
+
+int ptzba_schur_groups(ptzba_handle h, int32_t cap, int32_t* out4, int32_t* n_out) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  const int32_t n = (int32_t)(h->s2_groups_host.size() / 4);
+  if (n_out) *n_out = n;
+  for (int32_t k = 0; out4 && k < 4 * std::min(cap, n); ++k) out4[k] = h->s2_groups_host[k];
   return 0;
 }
 
@@ -2658,6 +2674,7 @@ static int solve_impl(ptzba_ctx* h, const double* lam_dev, int nx, const int* se
   BacksubArgs b;
   b.lm_seg_begin = h->lm_seg_begin.as<int32_t>();
   b.seg_frame = h->seg_frame.as<int32_t>();
+  b.seg_row = h->seg_row.as<int32_t>();
   b.w_slot = h->w_slot[c].p;
   b.lm_meta = h->lm_meta.as<int4>();
   b.lm_out = h->lm_out[c].as<double>();

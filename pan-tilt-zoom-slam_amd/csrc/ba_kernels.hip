@@ -609,8 +609,9 @@ void launch_build_prologue(double* S, int64_t ld, const int2* zt, int n_tiles, d
 // one wave per landmark (lanes over segments)
 // ------------------------------------------------------------------------------------------------
 // Trial state in one launch (with the trial's frame / ray tables, which the trial linearisation reads):
-// blocks [0, nb) back-substitute 4 landmarks each as above, the last block forms the trial poses, their
-// tables and the pose partials (one thread per frame, fixed-order reduction: identical on every rank).
+// block 0 forms the trial poses, their tables and the pose partials (one thread per frame, fixed-order reduction:
+// identical on every rank) -- first, so that its serial part runs under the landmark grid instead of after it --
+// and blocks [1, nb] back-substitute 4 landmarks each as above.
 struct PoseTrialArgs {
   const double* ptz;
   const double* g_pose;
@@ -628,7 +629,6 @@ template <typename real>
 __global__ __launch_bounds__(256) void k_trial(BacksubArgs a, PoseTrialArgs pa, FrameTab<double>* __restrict__ ft64,
                                                RayTab<double>* __restrict__ rt64, FrameTab<real>* __restrict__ ft,
                                                RayTab<real>* __restrict__ rt) {
-  const int nb = (a.n_lm + 3) / 4;
   // device-driven LM: current state and trial output by the decision's slot (BacksubArgs::state_xor)
   const bool sflip = a.sel && (((*a.sel) ^ a.state_xor) & 1);
   if (sflip) {
@@ -639,26 +639,40 @@ __global__ __launch_bounds__(256) void k_trial(BacksubArgs a, PoseTrialArgs pa, 
     a.rays = a.rays_trial;
     a.rays_trial = const_cast<double*>(u);
   }
-  if ((int)blockIdx.x == nb) {
-    const double lambda = a.lam_dev ? *a.lam_dev : a.lambda;
+  const double lambda = a.lam_dev ? *a.lam_dev : a.lambda;  // (with the up-front operands of either part)
+  if (blockIdx.x == 0) {
     __shared__ double red[4][256 / WAVE];
     double pr = 0, dx = 0, xx = 0, gm = 0;
     for (int f = threadIdx.x; f < pa.n_pose; f += blockDim.x) {
-      double x3[3];
+      // two round trips per frame: mask, pose, damping scale and system row together, then the row's step and
+      // gradient (a frame without a step reads row 0 and drops the values)
       const int fm = pa.fmask ? pa.fmask[f] : 3;
+      const int pos = a.frame_pos[f];
+      double x3[3], Dp[3], d3[3], gp[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
-        const double x = pa.ptz[3 * f + q];
+        x3[q] = pa.ptz[3 * f + q];
+        Dp[q] = pa.D_pose[3 * f + q];
+      }
+      const bool step = f >= a.n_fixed && (fm & 1);
+      const int k0 = f >= a.n_fixed ? max(pos, 0) : 0;  // system row (not through the mask: off its load's chain)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        d3[q] = a.dpose[k0 + q];
+        gp[q] = pa.g_pose[k0 + q];
+      }
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const double x = x3[q];
         if (fm & 2) xx += x * x;
         double y = x;
-        if (f >= a.n_fixed && (fm & 1)) {
-          const int k = a.frame_pos[f] + q;  // system row
-          const double d = a.dpose[k];
+        if (step) {
+          const double d = d3[q];
           y = x + d;
           if (fm & 2) {
-            pr += -0.5 * pa.g_pose[k] * d + 0.5 * lambda * pa.D_pose[3 * f + q] * d * d;
+            pr += -0.5 * gp[q] * d + 0.5 * lambda * Dp[q] * d * d;
             dx += d * d;
-            gm = fmax(gm, fabs(pa.g_pose[k]));
+            gm = fmax(gm, fabs(gp[q]));
           }
         }
         pa.ptz_trial[3 * f + q] = y;
@@ -689,60 +703,106 @@ __global__ __launch_bounds__(256) void k_trial(BacksubArgs a, PoseTrialArgs pa, 
     return;
   }
   const int lane = lane_id();
-  const int l = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (l >= a.n_lm) return;
+  // (a wave past the last landmark walks the last one again and its result is dropped: every wave reaches the
+  // workgroup's hand-over below)
+  const int wv = threadIdx.x >> 6;
+  const int l = min(((int)blockIdx.x - 1) * 4 + wv, a.n_lm - 1);
   const int s0 = a.lm_seg_begin[l], s1 = a.lm_seg_begin[l + 1];
   const bool alt = a.sel && *a.sel;  // device-chosen linearisation slot
   const real* __restrict__ w_slot = (const real*)(alt ? a.w_slot1 : a.w_slot);
   const int4 lmeta = a.lm_meta[l];
   // the landmark's own operands (independent of the segment walk) requested up front: the wave's dependent
-  // chain is segment list -> frame -> W slot / system row -> dpose, then the reduction and the stores
+  // chain is segment list -> (system row | frame) of two strides -> their W slots and dpose, then the reduction
+  // and the stores
   const double* lo = (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8;
   const double* vi = a.lm_aux + (int64_t)l * 8;
   const double g0 = lo[3], g1 = lo[4], v0 = vi[0], v1 = vi[1], v2 = vi[2];
   const double th = a.rays[2 * l], ph = a.rays[2 * l + 1];
   const double D0 = a.D_ray[2 * l], D1 = a.D_ray[2 * l + 1];
   double t0 = 0, t1 = 0;
-  for (int s = s0 + lane; s < s1; s += WAVE) {
-    const int f = a.seg_frame[s];
-    if (f < a.n_fixed) continue;
-    const double* dp = a.dpose + a.frame_pos[f];
-    real w[6];
-    slot_load6(w, w_slot + ((int64_t)lmeta.z + f - lmeta.x) * W_STRIDE);
+  // (lm_meta is used only inside the walk: pinned here, it is requested with lm_seg_begin instead of being moved
+  // under the walk's guard, where it was a round trip of its own)
+  asm volatile("" ::"v"(lmeta.x), "v"(lmeta.z));
+  // two strides of the segment list per trip, every load of a stage in flight together: a lane past the list reads
+  // the landmark's last segment and drops it, a segment of a fixed frame (seg_row < 0) reads row 0 and drops it.
+  // Per lane the sums run stride by stride as in a one-stride walk.
+  for (int sb = s0 + lane; sb - lane < s1; sb += 2 * WAVE) {
+    const int sc[2] = {min(sb, s1 - 1), min(sb + WAVE, s1 - 1)};
+    int row[2], fr[2];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      t0 += (double)w[2 * q] * dp[q];
-      t1 += (double)w[2 * q + 1] * dp[q];
+    for (int u = 0; u < 2; ++u) {
+      row[u] = a.seg_row[sc[u]];
+      fr[u] = a.seg_frame[sc[u]];
+    }
+    const bool ok[2] = {sb < s1 && row[0] >= 0, sb + WAVE < s1 && row[1] >= 0};
+    real w[2][6];
+    double dp[2][3];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      slot_load6(w[u], w_slot + ((int64_t)lmeta.z + fr[u] - lmeta.x) * W_STRIDE);
+      const double* d = a.dpose + max(row[u], 0);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) dp[u][q] = d[q];
+    }
+    // (selects, not branches: a load that only a branch uses is moved into it and its round trip comes back)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      double n0 = t0, n1 = t1;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        n0 += (double)w[u][2 * q] * dp[u][q];
+        n1 += (double)w[u][2 * q + 1] * dp[u][q];
+      }
+      t0 = ok[u] ? n0 : t0;
+      t1 = ok[u] ? n1 : t1;
     }
   }
   t0 = wave_total(t0);
   t1 = wave_total(t1);
+  // The step, the trial ray and its tables (fp64 tan / cos / sqrt / divisions: ~600 instructions) are one lane's
+  // work per landmark.  Run by the last lane of every wave they kept each SIMD's VALU busy for the whole launch;
+  // the four waves hand their landmark's operands over through LDS and lanes 0-3 of wave 0 run the tail once for
+  // all four (the same operations on the same values: the results are bit for bit the same).
+  __shared__ double tail[4][12];
   if (lane == WAVE - 1) {
-    double* red = a.lm_red + (int64_t)l * 4;
-    double nth = th, nph = ph;
-    if (s1 == s0) {
+    double* h = tail[wv];
+    h[0] = t0; h[1] = t1; h[2] = g0; h[3] = g1; h[4] = v0; h[5] = v1; h[6] = v2; h[7] = th; h[8] = ph; h[9] = D0;
+    h[10] = D1; h[11] = s1 == s0 ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  const int lt = ((int)blockIdx.x - 1) * 4 + (int)threadIdx.x;
+  if (threadIdx.x < 4 && lt < a.n_lm) {
+    const double* h = tail[threadIdx.x];
+    const double T0 = h[0], T1 = h[1], G0 = h[2], G1 = h[3], V0 = h[4], V1 = h[5], V2 = h[6], TH = h[7], PH = h[8];
+    const double DD0 = h[9], DD1 = h[10];
+    double* red = a.lm_red + (int64_t)lt * 4;
+    double nth = TH, nph = PH;
+    if (h[11] != 0.0) {
       red[0] = 0; red[1] = 0; red[2] = 0; red[3] = 0;
     } else {
-      const double r0 = g0 + t0, r1 = g1 + t1;
-      const double d0 = -(v0 * r0 + v1 * r1);
-      const double d1 = -(v1 * r0 + v2 * r1);
-      nth = th + d0;
-      nph = ph + d1;
-      const double lam = a.lam_dev ? *a.lam_dev : a.lambda;
-      red[0] = -0.5 * (g0 * d0 + g1 * d1) + 0.5 * lam * (D0 * d0 * d0 + D1 * d1 * d1);
-      red[1] = d0 * d0 + d1 * d1;
-      red[2] = th * th + ph * ph;
-      red[3] = fmax(fabs(g0), fabs(g1));
+      // delta = -Vinv r; pred = -1/2 g.delta + 1/2 lambda delta^T D delta.  Which product of a two-term sum the
+      // compiler fuses decides the last bit, and it chose otherwise here than in the one-lane-per-wave form of
+      // rounds 1-7: the fused operations are written out, as that form compiled (the trial state is bit for bit
+      // the same)
+      const double r0 = G0 + T0, r1 = G1 + T1;
+      const double d0 = -fma(V0, r0, V1 * r1);
+      const double d1 = -fma(V1, r0, V2 * r1);
+      nth = TH + d0;
+      nph = PH + d1;
+      red[0] = fma(fma(d0, DD0 * d0, (DD1 * d1) * d1), 0.5 * lambda, -(0.5 * fma(G1, d1, G0 * d0)));
+      red[1] = fma(d0, d0, d1 * d1);
+      red[2] = fma(TH, TH, PH * PH);
+      red[3] = fmax(fabs(G0), fabs(G1));
     }
-    a.rays_trial[2 * l] = nth;
-    a.rays_trial[2 * l + 1] = nph;
+    a.rays_trial[2 * lt] = nth;
+    a.rays_trial[2 * lt + 1] = nph;
     const RayTab<double> t = make_ray_tab<double>(nth, nph);
-    rt64[l] = t;
+    rt64[lt] = t;
     if constexpr (sizeof(real) != sizeof(double)) {
       RayTab<real> r;
       r.p0 = (real)t.p0; r.p1 = (real)t.p1; r.d0t = (real)t.d0t; r.d1t = (real)t.d1t; r.d1p = (real)t.d1p;
       r.pad0 = r.pad1 = r.pad2 = (real)0;
-      rt[l] = r;
+      rt[lt] = r;
     }
   }
 }
@@ -754,6 +814,24 @@ void launch_trial(const BacksubArgs& a, const double* ptz, const double* g_pose,
   PoseTrialArgs pa{ptz, g_pose, D_pose, ptz_trial, out4, n_pose, fmask, info};
   hipLaunchKernelGGL((k_trial<real>), dim3((unsigned)((a.n_lm + 3) / 4 + 1)), dim3(256), 0, st, a, pa,
                        (FrameTab<double>*)ft64, (RayTab<double>*)rt64, (FrameTab<real>*)ft, (RayTab<real>*)rt);
+}
+
+// static per-segment system row of k_trial's walk: frame_pos of the segment's frame, -1 for a fixed frame (one
+// load instead of the seg_frame -> frame_pos chain); rebuilt whenever frame_pos changes
+__global__ __launch_bounds__(256) void k_seg_row(const int32_t* __restrict__ seg_frame,
+                                                 const int32_t* __restrict__ frame_pos, int64_t n_seg, int n_fixed,
+                                                 int32_t* __restrict__ seg_row) {
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n_seg; s += (int64_t)gridDim.x * blockDim.x) {
+    const int f = seg_frame[s];
+    seg_row[s] = f < n_fixed ? -1 : frame_pos[f];
+  }
+}
+void launch_seg_row(const int32_t* seg_frame, const int32_t* frame_pos, int64_t n_seg, int n_fixed, int32_t* seg_row,
+                    hipStream_t st) {
+  if (n_seg <= 0) return;
+  const int64_t nb = (n_seg + 255) / 256;
+  hipLaunchKernelGGL(k_seg_row, dim3((unsigned)(nb < 8192 ? nb : 8192)), dim3(256), 0, st, seg_frame, frame_pos, n_seg,
+                     n_fixed, seg_row);
 }
 
 __device__ void lm_decide_body(LMDev* st, const double* scal, const double* __restrict__ loc,

@@ -156,6 +156,7 @@ struct SchurArgs {
 struct BacksubArgs {
   const int32_t* lm_seg_begin;
   const int32_t* seg_frame;
+  const int32_t* seg_row;  // [n_seg] frame_pos[seg_frame[s]], -1 for a fixed frame (launch_seg_row)
   const void* w_slot;    // [n_slot][W_STRIDE] real: W
   const int4* lm_meta;   // [n_lm] {first frame, last frame, slot offset, 0}
   const double* lm_out;
@@ -245,6 +246,9 @@ template <typename real>
 void launch_trial(const BacksubArgs& a, const double* ptz, const double* g_pose, const double* D_pose, double* ptz_trial,
                   double* out4, int n_pose, void* ft64, void* rt64, void* ft, void* rt, hipStream_t st,
                   const uint8_t* fmask = nullptr, const int* info = nullptr);
+// BacksubArgs::seg_row from seg_frame and frame_pos (both resident), once per problem
+void launch_seg_row(const int32_t* seg_frame, const int32_t* frame_pos, int64_t n_seg, int n_fixed, int32_t* seg_row,
+                    hipStream_t st);
 template <typename real>
 void launch_residual(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                      const void* rec_xy, const int64_t* perm, const void* ft64, const void* rt64, double u, double v,

@@ -985,6 +985,12 @@ __device__ __forceinline__ real part_load(const real* p) {
   if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else return *p;
 }
+// lane `lane`'s copy of v (wave-uniform lane index; reads the register whether or not that lane is still active)
+__device__ __forceinline__ double lane_read(double v, int lane) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
 template <typename real, bool AGENT>
 __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4 g, int e) {
   constexpr int NE = SF * 9 * WAVE;
@@ -996,45 +1002,82 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
   const int f1c = min(f1, a.n_pose - 1), f2c = min(f2, a.n_pose - 1);
   const int whi = a.frame_win_hi[f1c];
   const int64_t col0 = a.frame_pos[f1c], pf2 = a.frame_pos[f2c];
-  if (!(f1 < a.n_pose && f2 >= f1 && f2 <= whi)) return;
-  const real* p = (const real*)a.part + e;
+  // chunk 0: the wave's one diagonal lane (f2 == f1; i, q, r are wave-uniform) adds U of the frame over the tile's
+  // splits.  The wave requests them for it in the same round trip, lane u the value of split u (clamped), and the
+  // diagonal lane takes them in item order by lane reads below: one load and two registers in place of one
+  // dependent load per split in one lane.
+  const int last = g.w - 1;  // (a group has at least one split)
+  const int ui = q <= r ? (q == 0 ? r : (q == 1 ? 2 + r : 5)) : (r == 0 ? q : (r == 1 ? 2 + q : 5));
+  const double* pd = a.part_diag + (int64_t)i * 12 + ui;
+  const bool tile0 = chunk == 0 && f1 < a.n_pose;  // (wave-uniform)
+  double uc = 0;
+  if (tile0) uc = part_load<double, AGENT>(pd + (int64_t)min(g.z + ln, last) * (SF * 12));
+  // (the fused prepare's damping operands of the diagonal lane: with the same round trip)
+  const bool damp = a.prep.pad && q == r && f2 == f1;
+  double Dv = 0, lambda = 0;
+  if (damp) {
+    lambda = a.prep.lam_dev ? *a.prep.lam_dev : a.prep.lambda;
+    Dv = a.prep.D_pose[3 * (int64_t)f1c + q];
+  }
+  const bool in = f1 < a.n_pose && f2 >= f1 && f2 <= whi;
   double v = 0;
-  int it = g.z;
-  // up to 8 splits' partials in flight (a tile has ~8 at config 3: one round trip), summed in item order
-  for (; it + 8 <= g.w; it += 8) {
-    double x[8];
+  if (in) {
+    // the splits' partials in batches of 8 with the next batch requested before this one is summed (a tile of up
+    // to 16 splits: one round trip), branch-free: an index past the group reads the group's last split and is
+    // dropped.  Summed in item order.
+    const real* p = (const real*)a.part;  // (uniform split base + the thread's element)
+    real x[8], y[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = part_load<real, AGENT>(p + (int64_t)(it + u) * NE);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v += x[u];
-  }
-  if (it < g.w) {
-    double x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) x[u] = it + u < g.w ? (double)part_load<real, AGENT>(p + (int64_t)(it + u) * NE) : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (it + u < g.w) v += x[u];
-  }
-  if (f2 == f1) {  // chunk 0: U of the frame, summed over the tile's splits
-    const int ui = q <= r ? (q == 0 ? r : (q == 1 ? 2 + r : 5)) : (r == 0 ? q : (r == 1 ? 2 + q : 5));
-    double du = 0;  // diag U as the chunk-0 vector block sums it (fresh, item order): the damping's scale
-    for (int it2 = g.z; it2 < g.w; ++it2) {
-      const double uu = part_load<double, AGENT>(a.part_diag + ((int64_t)it2 * SF + i) * 12 + ui);
-      v += uu;
-      du += uu;
+    for (int u = 0; u < 8; ++u) {
+      x[u] = part_load<real, AGENT>(p + (int64_t)min(g.z + u, last) * NE + (unsigned)e);
+      y[u] = 0;
     }
-    if (a.prep.pad && q == r) {  // fused prepare: Marquardt damping of the pose row (k_chol_prepare's rule)
-      const double lambda = a.prep.lam_dev ? *a.prep.lam_dev : a.prep.lambda;
-      double* D = a.prep.D_pose + 3 * (int64_t)f1 + q;
-      const double d = fmax(*D, fmax(du, 1e-12));
-      *D = d;
+    if (g.z + 8 < g.w) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) y[u] = part_load<real, AGENT>(p + (int64_t)min(g.z + 8 + u, last) * NE + (unsigned)e);
+    }
+    for (int it = g.z;;) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (it + u < g.w) v += (double)x[u];
+      it += 8;
+      if (it >= g.w) break;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = y[u];
+      if (it + 8 < g.w) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          y[u] = part_load<real, AGENT>(p + (int64_t)min(it + 8 + u, last) * NE + (unsigned)e);
+      }
+    }
+  }
+  if (tile0) {  // (the whole wave again: the lane reads see every lane's value)
+    const bool diag = in && f2 == f1;
+    double du = 0;  // diag U as the chunk-0 vector block sums it (fresh, item order): the damping's scale
+    const int nw = min(g.w - g.z, WAVE);
+    for (int u = 0; u < nw; ++u) {
+      const double uu = lane_read(uc, u);
+      if (diag) {
+        v += uu;
+        du += uu;
+      }
+    }
+    if (diag)
+      for (int it2 = g.z + WAVE; it2 < g.w; ++it2) {  // (a tile of more than 64 splits: the rest one by one)
+        const double uu = part_load<double, AGENT>(pd + (int64_t)it2 * (SF * 12));
+        v += uu;
+        du += uu;
+      }
+    if (diag && damp) {  // fused prepare: Marquardt damping of the pose row (k_chol_prepare's rule)
+      const double d = fmax(Dv, fmax(du, 1e-12));
+      a.prep.D_pose[3 * (int64_t)f1 + q] = d;
       const int64_t row = col0 + q;
       a.S[row * a.ld + row] = v;
       a.S[row * a.ld + row] += lambda * d;
       return;
     }
   }
+  if (!in) return;
   const int64_t ld = a.ld;
   if (pf2 >= col0) a.S[(pf2 + r) * ld + col0 + q] = v;
   else a.S[(col0 + q) * ld + pf2 + r] = v;
@@ -1042,17 +1085,40 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
 template <bool AGENT>
 __device__ __forceinline__ void schur_reduce_vec(const SchurArgs& a, const int4 g, int tid) {
   const int f1b = g.x;
-  const int i2 = tid / 3, q2 = tid - 3 * i2, f = f1b + i2;
+  // threads [0, 3 SF): g_pose and sum W V~^-1 g of (frame, q2) -> b, g_pose; threads [3 SF, 6 SF): diag U -> dU.
+  // Each of a frame's 12 values is a sum of its own (split by split in item order), so a thread reads only the
+  // ones it writes: eight splits in flight with clamped indices, the system row with the first batch.
+  const bool diag = tid >= SF * 3;
+  const int t = diag ? tid - SF * 3 : tid;
+  const int i2 = t / 3, q2 = t - 3 * i2, f = f1b + i2;
   if (f >= a.n_pose) return;
-  double d[12];
-  for (int k = 0; k < 12; ++k) d[k] = 0;
-  for (int it2 = g.z; it2 < g.w; ++it2)
-    for (int k = 0; k < 12; ++k) d[k] += part_load<double, AGENT>(a.part_diag + ((int64_t)it2 * SF + i2) * 12 + k);
   const int c0 = a.frame_pos[f];
-  const double bv = -d[6 + q2] + d[9 + q2];
+  const int last = g.w - 1;
+  const int k0 = diag ? (q2 == 0 ? 0 : (q2 == 1 ? 3 : 5)) : 6 + q2;
+  const double* pd = a.part_diag + (int64_t)i2 * 12 + k0;
+  double d0 = 0, d1 = 0;  // value k0 and (g_pose threads) value k0 + 3
+  for (int it2 = g.z; it2 < g.w; it2 += 8) {
+    double x0[8], x1[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const double* ps = pd + (int64_t)min(it2 + u, last) * (SF * 12);
+      x0[u] = part_load<double, AGENT>(ps);
+      x1[u] = part_load<double, AGENT>(diag ? ps : ps + 3);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (it2 + u < g.w) {
+        d0 += x0[u];
+        d1 += x1[u];
+      }
+  }
+  if (diag) {
+    a.dU[c0 + q2] = d0;
+    return;
+  }
+  const double bv = -d0 + d1;
   a.b[c0 + q2] = bv;
-  a.g_pose[c0 + q2] = d[6 + q2];
-  a.dU[c0 + q2] = d[q2 == 0 ? 0 : (q2 == 1 ? 3 : 5)];
+  a.g_pose[c0 + q2] = d0;
   if (a.prep.pad) a.S[a.prep.n_aug * a.ld + c0 + q2] = bv;  // fused prepare: the augmented row b^T
 }
 
@@ -1064,11 +1130,11 @@ __device__ __forceinline__ void schur_reduce_vec(const SchurArgs& a, const int4 
 // fp32 partials: thread = four elements of a tile (grid: tile x 18 blocks of 256); fp64: one element
 // (tile x 72 blocks).
 template <typename real>
-__global__ __launch_bounds__(256) void k_schur_reduce(SchurArgs a) {
+__global__ __launch_bounds__(256, sizeof(real) == 4 ? 8 : 6) void k_schur_reduce(SchurArgs a) {
   if (a.skip_if && *a.skip_if) return;
   const int4 g = a.groups[blockIdx.y];  // {f1b, chunk, first item, end item}
   schur_reduce_elem<real, false>(a, g, blockIdx.x * 256 + threadIdx.x);
-  if (g.y == 0 && blockIdx.x == 0 && threadIdx.x < SF * 3) schur_reduce_vec<false>(a, g, threadIdx.x);
+  if (g.y == 0 && blockIdx.x == 0 && threadIdx.x < SF * 6) schur_reduce_vec<false>(a, g, threadIdx.x);
 }
 
 template <typename real>
