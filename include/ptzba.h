@@ -173,6 +173,12 @@ PTZBA_EXPORT int ptzba_k2_info(ptzba_handle h, int* info8);
  * fewest / most splits of a tile, [3] tiles with at least 9 splits (the eight-in-flight loop and its remainder),
  * [4] the highest chunk index, [5] tiles whose partner range f1b + 64 (chunk + 1) passes n_pose; [6], [7] zero */
 PTZBA_EXPORT int ptzba_k2_tile_info(ptzba_handle h, int32_t* out8);
+/* host only (ptzba_version 0.7): which launch path the handle's reduced-system builds took since ptzba_set_problem:
+ * [0] builds enqueued with the prologue launch in front (zeroing + landmark damping: the host-step API, fp64,
+ * PTZBA_K2_PIPE=0, pose / marginal priors, PTZBA_NO_FUSED_PREP, covariance, ranks), [1] builds whose prologue is
+ * folded into the reduced-system kernel and the trial kernel (device-driven single-GPU fp32 solves), [2] 1 when
+ * PTZBA_K2_PROLOGUE=1 forces the prologue launch for every build, [3] zero */
+PTZBA_EXPORT int ptzba_build_info(ptzba_handle h, int64_t* out4);
 /* host phase times of the last ptzba_set_problem (sort, segments, K2 structure, plan, uploads ...): names[k] (static
  * strings) and ms[k] for k < min(cap, *n_out); *n_out = the number of phases recorded */
 PTZBA_EXPORT int ptzba_setup_timing(ptzba_handle h, int32_t cap, const char** names, double* ms, int32_t* n_out);

@@ -69,6 +69,8 @@ struct ptzba_ctx {
   int n_s2_items = 0, n_s2_groups = 0;
   int k2_pipe = 1;     // fp32 K2 kernel: 1 producer / consumer waves (waves 0-3 stage), 2 (even waves stage), 0 k_schur_mf
   int k2_info[8] = {};  // ptzba_k2_info
+  bool k2_prologue = false;  // PTZBA_K2_PROLOGUE=1: every build launches k_build_prologue (A/B, tests)
+  int64_t n_build_prologue = 0, n_build_folded = 0;  // builds enqueued on either path (ptzba_build_info)
   int k2_tile_info[8] = {};  // ptzba_k2_tile_info
   std::vector<int32_t> s2_groups_host;  // ptzba_schur_groups: the tiles' {f1b, chunk, first item, end item}
   int64_t n_slot = 0;  // dense landmark x frame slots (W table rows)
@@ -312,9 +314,10 @@ const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.4: ptzba_set_pose_priors / ptzba_pose_priors (sized by struct_size) / ptzba_pose_prior_info.
 // 0.5: ptzba_marginal_prior / ptzba_set_marginal_prior / ptzba_marginal_prior_info (structs sized by struct_size).
 // 0.6: ptzba_set_ray_priors / ptzba_ray_priors (sized by struct_size) / ptzba_ray_prior_info.
+// 0.7: ptzba_build_info (read-only counters of the builds' launch path).
 const char* ptzba_version(void) {
-  return "ptzba 0.6 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
-         "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors)";
+  return "ptzba 0.7 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
+         "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors as 0.6; ptzba_build_info)";
 }
 
 ptzba_handle ptzba_new(int device) {
@@ -1835,6 +1838,9 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
     // PTZBA_K2_PIPE=0: the block-synchronous k_schur_mf (kept for one round: A/B and the bitwise parity test);
     // =even: the even waves stage instead of waves 0-3
     h->k2_pipe = getenv_is("PTZBA_K2_PIPE", "0") ? 0 : (getenv_is("PTZBA_K2_PIPE", "even") ? 2 : 1);
+    // PTZBA_K2_PROLOGUE=1: keep the k_build_prologue launch in front of every build (build_impl)
+    h->k2_prologue = getenv_is("PTZBA_K2_PROLOGUE", "1");
+    h->n_build_prologue = h->n_build_folded = 0;
     {
       std::vector<uint8_t> cov((n_pose + SCHUR_F1) / SCHUR_F1 + 1, 0);
       for (size_t g = 0; g < s2_groups.size(); g += 4)
@@ -2163,6 +2169,16 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
 int ptzba_k2_info(ptzba_handle h, int* out) {
   if (!h || !h->have_problem) return fail("no problem set");
   for (int k = 0; k < 8; ++k) out[k] = h->k2_info[k];
+  return 0;
+}
+
+int ptzba_build_info(ptzba_handle h, int64_t* out4) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!out4) return fail("bad arguments");
+  out4[0] = h->n_build_prologue;
+  out4[1] = h->n_build_folded;
+  out4[2] = h->k2_prologue ? 1 : 0;
+  out4[3] = 0;
   return 0;
 }
 
@@ -2543,10 +2559,17 @@ static int build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   // system raw for callers that sum it between build and solve (include/ptzba.h, the round-2 protocol)
   if (sel && h->fused_prep())
     fp = FusedPrep{h->row_pad.as<uint8_t>(), h->n_aug, h->info.as<int>(), h->D_pose.as<double>(), lambda, lam_dev};
-  launch_build_prologue(h->S(), h->ld, h->ztiles.as<int2>(), h->n_ztiles, h->bvec(), 3 * h->ld,
-                        h->lm_out[c].as<double>(), h->lm_seg_begin.as<int32_t>(), h->D_ray.as<double>(),
-                        h->lm_aux.as<double>(), h->n_lm, lambda, lam_dev, skip_if, h->st, h->lm_out[1].as<double>(),
-                        sel, fp);
+  // Device-driven single-GPU fp32 builds on the producer / consumer K2 need no prologue launch: K2 zeroes the
+  // pattern tiles, the vectors and info itself and forms the landmark damping in its list build, k_trial forms its
+  // own and keeps D_ray (SchurArgs::ztiles, lm_damp).  Every other build launches the prologue as before.
+  const bool fold = sel && fp.pad && h->precision == PTZBA_FP32 && h->k2_pipe != 0 && !h->k2_prologue &&
+                    h->n_s2_items > 0 && h->n_pose - h->n_fixed > 0;
+  if (!fold)
+    launch_build_prologue(h->S(), h->ld, h->ztiles.as<int2>(), h->n_ztiles, h->bvec(), 3 * h->ld,
+                          h->lm_out[c].as<double>(), h->lm_seg_begin.as<int32_t>(), h->D_ray.as<double>(),
+                          h->lm_aux.as<double>(), h->n_lm, lambda, lam_dev, skip_if, h->st, h->lm_out[1].as<double>(),
+                          sel, fp);
+  ++(fold ? h->n_build_folded : h->n_build_prologue);
   SchurArgs a;
   a.items = h->s2_items.as<int4>();
   a.groups = h->s2_groups.as<int4>();
@@ -2569,6 +2592,13 @@ static int build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   a.w_slot1 = h->w_slot[1].p;
   a.sel = sel;
   a.prep = fp;
+  a.ztiles = fold ? h->ztiles.as<int2>() : nullptr;
+  a.n_ztiles = h->n_ztiles;
+  a.vec = h->bvec();
+  a.n_vec = 3 * h->ld;
+  a.lm_out = h->lm_out[c].as<double>();
+  a.lm_out1 = h->lm_out[1].as<double>();
+  a.D_ray = h->D_ray.as<double>();
   tm_begin(h, TM_SCHUR);
   if (h->precision == PTZBA_FP32)
     launch_schur<float>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, h->k2_pipe);

@@ -714,9 +714,11 @@ __global__ __launch_bounds__(256) void k_trial(BacksubArgs a, PoseTrialArgs pa, 
   // the landmark's own operands (independent of the segment walk) requested up front: the wave's dependent
   // chain is segment list -> (system row | frame) of two strides -> their W slots and dpose, then the reduction
   // and the stores
+  // (the damped block V~^-1 is formed in the tail below from the landmark's row, D_ray and lambda -- lm_damp, the
+  // build prologue's own expressions -- so the kernel does not depend on who wrote lm_aux: device-driven single-GPU
+  // builds fold the prologue into K2 and write none)
   const double* lo = (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8;
-  const double* vi = a.lm_aux + (int64_t)l * 8;
-  const double g0 = lo[3], g1 = lo[4], v0 = vi[0], v1 = vi[1], v2 = vi[2];
+  const double g0 = lo[3], g1 = lo[4], v0 = lo[0], v1 = lo[1], v2 = lo[2];
   const double th = a.rays[2 * l], ph = a.rays[2 * l + 1];
   const double D0 = a.D_ray[2 * l], D1 = a.D_ray[2 * l + 1];
   double t0 = 0, t1 = 0;
@@ -773,13 +775,18 @@ __global__ __launch_bounds__(256) void k_trial(BacksubArgs a, PoseTrialArgs pa, 
   const int lt = ((int)blockIdx.x - 1) * 4 + (int)threadIdx.x;
   if (threadIdx.x < 4 && lt < a.n_lm) {
     const double* h = tail[threadIdx.x];
-    const double T0 = h[0], T1 = h[1], G0 = h[2], G1 = h[3], V0 = h[4], V1 = h[5], V2 = h[6], TH = h[7], PH = h[8];
-    const double DD0 = h[9], DD1 = h[10];
+    const double T0 = h[0], T1 = h[1], G0 = h[2], G1 = h[3], TH = h[7], PH = h[8];
     double* red = a.lm_red + (int64_t)lt * 4;
     double nth = TH, nph = PH;
     if (h[11] != 0.0) {
       red[0] = 0; red[1] = 0; red[2] = 0; red[3] = 0;
     } else {
+      // the landmark's damping, and its scale memory D_ray <- d (idempotent: after a build whose prologue launch
+      // stored d already this rewrites the value it read)
+      const LmDamp dm = lm_damp(h[4], h[5], h[6], G0, G1, h[9], h[10], lambda);
+      const double V0 = dm.i00, V1 = dm.i01, V2 = dm.i11, DD0 = dm.d0, DD1 = dm.d1;
+      a.D_ray[2 * lt] = DD0;
+      a.D_ray[2 * lt + 1] = DD1;
       // delta = -Vinv r; pred = -1/2 g.delta + 1/2 lambda delta^T D delta.  Which product of a two-term sum the
       // compiler fuses decides the last bit, and it chose otherwise here than in the one-lane-per-wave form of
       // rounds 1-7: the fused operations are written out, as that form compiled (the trial state is bit for bit

@@ -115,7 +115,8 @@ struct LinArgs {
 // splits of a tile's landmark list.  Static structure built once by ptzba_set_problem.
 constexpr int SCHUR_F1 = 32;
 constexpr int SCHUR_LMAX = 512;  // landmarks per work item (split size cap)
-// Single-GPU builds fold k_chol_prepare into the build: the prologue writes the constant diagonal entries
+// Single-GPU builds fold k_chol_prepare into the build: the prologue (or K2 in its place, SchurArgs::ztiles) writes the
+// constant diagonal entries
 // (padding identity, augmented diagonal, identity below it) and resets info; k_schur_reduce writes the
 // augmented row b^T and the pose damping (D_pose = max(D_pose, diag U); S_ff += lambda D_pose), the same
 // values in the same order as the prepare launch.  pad == nullptr: not fused (multi-rank exchanges need the
@@ -128,6 +129,33 @@ struct FusedPrep {
   double lambda;
   const double* lam_dev;
 };
+
+// Landmark damping (k_build_prologue's rule) for the kernels that form it themselves instead of reading lm_aux:
+// d = max(D_ray, max(diag V, 1e-12)), V~ = V + lambda diag(d), V~^-1 and V~^-1 g.  The fused operations are written
+// out exactly as the prologue compiles (contraction is off inside, so nothing else fuses): every caller gets the
+// prologue's bits from the same inputs.  in: the landmark's lm_out row (V00 V01 V11 g0 g1 ...).
+struct LmDamp {
+  double d0, d1;          // the damping scales (what the prologue stores to D_ray)
+  double i00, i01, i11;   // V~^-1 (zero when V~ is not positive definite)
+  double vg0, vg1;        // V~^-1 g
+};
+__device__ __forceinline__ LmDamp lm_damp(double V00, double V01, double V11, double g0, double g1, double D0,
+                                          double D1, double lambda) {
+#pragma clang fp contract(off)
+  LmDamp r;
+  r.d0 = fmax(D0, fmax(V00, 1e-12));
+  r.d1 = fmax(D1, fmax(V11, 1e-12));
+  const double a = fma(lambda, r.d0, V00), c = fma(lambda, r.d1, V11);
+  const double det = fma(a, c, -(V01 * V01));
+  r.i00 = 0; r.i01 = 0; r.i11 = 0;
+  if (det > 0 && isfinite(det)) {
+    const double id = 1.0 / det;
+    r.i00 = c * id; r.i01 = -V01 * id; r.i11 = a * id;
+  }
+  r.vg0 = fma(r.i00, g0, r.i01 * g1);
+  r.vg1 = fma(r.i01, g0, r.i11 * g1);
+  return r;
+}
 
 struct SchurArgs {
   const int4* items;              // [n_items] {f1b, chunk, list begin, list end}
@@ -151,6 +179,17 @@ struct SchurArgs {
   const void* w_slot1;
   const int* sel;
   FusedPrep prep;                 // single-GPU: the prepare's augmented row and damping (pad != nullptr)
+  // Folded prologue (device-driven single-GPU fp32 builds, k_schur_mfp only; ztiles == nullptr: k_build_prologue ran):
+  // the kernel zeroes the pattern tiles, vec and info[0] itself (the product waves of item i: tiles i, i + n_items,
+  // ...; item 0 also vec) and forms the landmark damping in its list build from lm_out / D_ray / lambda (prep.lam_dev)
+  // instead of reading lm_aux.  It writes neither lm_aux nor D_ray (k_trial stores D_ray).
+  const int2* ztiles;             // [n_ztiles] the factor pattern's tiles
+  int n_ztiles;
+  double* vec;                    // b | g_pose | dU
+  int64_t n_vec;
+  const double* lm_out;           // [n_lm][8] K1's landmark rows of slot 0 / 1 (sel)
+  const double* lm_out1;
+  const double* D_ray;            // [2 n_lm]
 };
 
 struct BacksubArgs {
@@ -160,8 +199,8 @@ struct BacksubArgs {
   const void* w_slot;    // [n_slot][W_STRIDE] real: W
   const int4* lm_meta;   // [n_lm] {first frame, last frame, slot offset, 0}
   const double* lm_out;
-  const double* lm_aux;
-  const double* D_ray;
+  const double* lm_aux;  // (not read by k_trial: it forms the damped block itself, see lm_damp)
+  double* D_ray;         // [2 n_lm] the landmarks' damping scales; k_trial stores max(D_ray, max(diag V, 1e-12))
   const double* dpose;   // [n_aug] system order
   const int32_t* frame_pos;
   const double* rays;    // [2 n_lm]

@@ -636,6 +636,11 @@ __global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
 // either side needs only signals of batches < b from the other side (s_ready of b needs s_done of
 // b - MF_RING, which needs s_ready of b - MF_RING): the dependency chain ends at batch 0, which waits for
 // nothing.  No wait looks at global memory or at another workgroup.
+// Folded build prologue (SchurArgs::ztiles != nullptr: device-driven single-GPU builds, api.hip build_impl): the
+// launch also does k_build_prologue's work, so that launch is not needed.  The list build forms V~^-1, g_l and
+// V~^-1 g from K1's landmark row, D_ray and lambda (lm_damp: the prologue's fp64 expressions; it only reads), and the
+// product waves, idle until the first batch is staged, zero the pattern tiles of S, b | g_pose | dU and info[0].
+// A launch that leaves at skip_if zeroes nothing: the next solve's first build zeroes for itself.
 // ------------------------------------------------------------------------------------------------
 #ifndef MF_RING
 #define MF_RING 2  // operand buffers in the ring (2: 116 KB of LDS; 3: 159 KB, measured no faster)
@@ -711,10 +716,26 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
   const int f2base = f1b + WAVE * chunk;
   const bool alt = a.sel && *a.sel;  // device-chosen linearisation slot
   const float* __restrict__ w_slot = (const float*)(alt ? a.w_slot1 : a.w_slot);
+  // folded prologue (SchurArgs::ztiles): the damped landmark blocks are formed here from K1's rows, D_ray and lambda
+  // (read-only: nothing of them is written by this launch) instead of being read from lm_aux -- lm_damp gives the
+  // prologue's own bits
+  const bool fold = a.ztiles != nullptr;  // (uniform over the launch)
+  const double* __restrict__ lm_rows = alt ? a.lm_out1 : a.lm_out;
+  const double lambda = fold ? (a.prep.lam_dev ? *a.prep.lam_dev : a.prep.lambda) : 0.0;
   for (int k = t; k < nl; k += 512) {
     const int4 m = a.item_lm[lb + k];
     sL[k] = m;
-    const double* vi = a.lm_aux + (int64_t)m.x * 8;
+    double vi[5];
+    if (fold) {
+      const double* in = lm_rows + (int64_t)m.x * 8;
+      const LmDamp d = lm_damp(in[0], in[1], in[2], in[3], in[4], a.D_ray[2 * (int64_t)m.x],
+                               a.D_ray[2 * (int64_t)m.x + 1], lambda);
+      vi[0] = d.i00; vi[1] = d.i01; vi[2] = d.i11; vi[3] = d.vg0; vi[4] = d.vg1;
+    } else {
+      const double* p = a.lm_aux + (int64_t)m.x * 8;
+#pragma unroll
+      for (int q = 0; q < 5; ++q) vi[q] = p[q];
+    }
     int e = 0;
     (void)frexp(vi[0] + vi[2], &e);
     const float g = ldexpf(1.f, e / 2);
@@ -904,6 +925,35 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
     // ---- product waves: row blocks 3 rg.., column blocks 6 cg.. ----
     const int rg = rk >> 1, cg = rk & 1;
     const int fr = lane & 15, fk = (lane >> 4) * 8;  // fragment row / column and k offset of this lane
+    if (fold) {
+      // folded prologue: while the first batch is staged, these 256 threads zero the factor pattern's tiles item,
+      // item + n_items, ... with k_build_prologue's stores (the fused prepare's constant diagonal entries included),
+      // item 0 also b | g_pose | dU and info[0].  This launch touches S and the vectors nowhere else (the partials
+      // go to part / part_diag; k_schur_reduce, the next launch, writes S), and the previous factor's last reader
+      // finished before the launch started.
+      const int pt = rk * WAVE + lane;
+      for (int tz = item; tz < a.n_ztiles; tz += (int)gridDim.x) {
+        const int2 tij = a.ztiles[tz];
+        double* T = a.S + (int64_t)tij.x * CHOL_NB * a.ld + (int64_t)tij.y * CHOL_NB;
+        const bool diag_tile = a.prep.pad && tij.x == tij.y;
+        for (int e = pt; e < CHOL_NB * CHOL_NB / 2; e += 4 * WAVE) {
+          const int row = e >> 4, c0 = 2 * (e & 15);
+          double2 v = make_double2(0.0, 0.0);
+          if (diag_tile && (row == c0 || row == c0 + 1)) {
+            const int64_t r = (int64_t)tij.x * CHOL_NB + row;
+            double dv;
+            if (r < a.prep.n_aug) dv = a.prep.pad[r] ? 1.0 : 0.0;
+            else dv = r == a.prep.n_aug ? 1e300 : 1.0;
+            if (row == c0) v.x = dv; else v.y = dv;
+          }
+          *reinterpret_cast<double2*>(T + (int64_t)row * a.ld + c0) = v;
+        }
+      }
+      if (item == 0) {
+        for (int64_t e = pt; e < a.n_vec; e += 4 * WAVE) a.vec[e] = 0.0;
+        if (a.prep.pad && pt == 0) a.prep.info[0] = 0;
+      }
+    }
     f4v c[3][6];  // fp32 over all the item's batches (see k_schur_mf)
 #pragma unroll
     for (int x = 0; x < 3; ++x)

@@ -161,6 +161,7 @@ def lib():
         "ptzba_k1_info": ([V, V], I),
         "ptzba_k2_info": ([V, V], I),
         "ptzba_k2_tile_info": ([V, V], I),
+        "ptzba_build_info": ([V, V], I),
         "ptzba_schur_groups": ([V, I32, V, V], I),
         "ptzba_solver_info": ([V, V], I),
         "ptzba_residual": ([V, V, V], I),
@@ -272,7 +273,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "ptzba_new", "ptzba_delete", "ptzba_last_error", "ptzba_version", "ptzba_set_stream", "ptzba_use_own_stream", "ptzba_set_problem",
-    "ptzba_problem_info", "ptzba_k1_info", "ptzba_k2_info", "ptzba_k2_tile_info", "ptzba_schur_groups", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
+    "ptzba_problem_info", "ptzba_k1_info", "ptzba_k2_info", "ptzba_k2_tile_info", "ptzba_build_info", "ptzba_schur_groups", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
     "ptzba_build_reduced", "ptzba_solve_reduced", "ptzba_step", "ptzba_set_huber_curvature", "ptzba_set_setup_front", "ptzba_setup_timing", "ptzba_solve", "ptzba_solve_resident", "ptzba_read_scalars", "ptzba_accept",
     "ptzba_lm_start", "ptzba_lm_init", "ptzba_lm_build", "ptzba_lm_solve", "ptzba_lm_decide", "ptzba_lm_wait",
     "ptzba_exchange", "ptzba_exchange_packed", "ptzba_pack", "ptzba_unpack", "ptzba_sync", "ptzba_kernel_times", "ptzba_reset_kernel_times", "ptzba_comm_times", "ptzba_dist_form_estimate", "ptzba_save_state", "ptzba_restore_state", "ptz_ray_to_image",
@@ -1427,6 +1428,14 @@ class BAHandle:
         _check(lib().ptzba_k2_tile_info(self.h, _ptr(out)), "ptzba_k2_tile_info")
         keys = ["tiles", "splits_min", "splits_max", "tiles_ge9_splits", "chunk_max", "tiles_past_n_pose"]
         return dict(zip(keys, [int(x) for x in out[:6]]))
+
+    def build_info(self):
+        """Which launch path the reduced-system builds took since set_problem (ptzba_build_info): builds with the
+        prologue launch in front, builds with the prologue folded into K2 and the trial kernel, and whether
+        PTZBA_K2_PROLOGUE=1 forces the launch."""
+        out = np.zeros(4, np.int64)
+        _check(lib().ptzba_build_info(self.h, _ptr(out)), "ptzba_build_info")
+        return dict(prologue_builds=int(out[0]), folded_builds=int(out[1]), forced_prologue=bool(out[2]))
 
     def schur_groups(self):
         """The reduced-system kernel's tiles (ptzba_schur_groups): an int32 array [tiles, 4] of {first frame of the
