@@ -296,6 +296,21 @@ typedef struct {
 } ptzba_cov_opts;
 PTZBA_EXPORT int ptzba_covariance(ptzba_handle h, const ptzba_cov_opts* opts, double* pose_cov,
                                   const int32_t* lm_index, int32_t n_lm, double* ray_cov, double* info);
+/* Joint posterior covariance of chosen parameters (ptzba_version 0.8): the dense sub-matrix of scale * H^-1, H as
+ * ptzba_covariance (priors included), cut at the given frames and landmarks.  Parameter order: frames[0 .. n_frame)
+ * first, (pan, tilt, f) each, then landmarks[0 .. n_lm), (theta, phi) each, both in the given order; with n_frame == 1
+ * this is the EKF state layout.  cov_out [n][n] row-major, n = 3 n_frame + 2 n_lm, symmetric bit for bit.  A fixed
+ * frame and a landmark without records get all-zero rows and columns.  The diagonal 3 x 3 / 2 x 2 blocks are the
+ * blocks ptzba_covariance returns; the cross blocks carry the correlations it drops, e.g. the covariance of the
+ * relative pose of two frames, S_aa + S_bb - S_ab - S_ba.
+ * opts, info and the between-solves contract are ptzba_covariance's (no side effect on a following solve).  Refused
+ * with nothing written and the handle left as it was: an unknown struct_size, a frame or landmark out of range or
+ * named twice, n < 1 or n > PTZBA_COV_JOINT_MAX_COLS, a NULL cov_out, a pending LM trial, a sharded handle or one
+ * with a communicator or hook attached, an undamped system that is not positive definite. */
+#define PTZBA_COV_JOINT_MAX_COLS 2048
+PTZBA_EXPORT int ptzba_covariance_joint(ptzba_handle h, const ptzba_cov_opts* opts, const int32_t* frames,
+                                        int32_t n_frame, const int32_t* landmarks, int32_t n_lm, double* cov_out,
+                                        double* info);
 /* Gaussian pose priors (ptzba_version 0.4).  A prior is a list of factors; factor k names G_k distinct free frames
  * (1 <= G_k <= 8), a mean mu_k of 3 G_k values and a symmetric positive semi-definite information matrix Lambda_k of
  * size 3 G_k x 3 G_k, per frame in the order pan, tilt, f.  The objective becomes

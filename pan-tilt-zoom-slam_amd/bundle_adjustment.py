@@ -130,7 +130,9 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
     (row l belongs to landmarks[l]) and `info`: the posterior covariance blocks (J^T J)^-1 at the returned solution
-    (ptzba.BAHandle.covariance; with loss='huber' the IRLS-weighted normal matrix).
+    (ptzba.BAHandle.covariance; with loss='huber' the IRLS-weighted normal matrix).  covariance={"joint": (frames,
+    landmarks)} -- positions in `images` and landmark ids -- adds `joint` (also `info["joint"]`), the dense joint covariance of those
+    parameters (ptzba.BAHandle.covariance_joint: frames first, 3 each, then landmarks, 2 each).
     pose_priors (keyword only; off: the call and its outputs are unchanged): Gaussian pose prior factors
     [(image indices, mean, info), ...] keyed by image index (entries of image_indices) -- ptzba.check_pose_priors'
     factor form, 1/2 e^T info e with e = the named images' (pan, tilt, f) minus mean, added to the objective.  A factor
@@ -264,17 +266,22 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     marg_out = dict(marginal=None, stats={})  # (no records: nothing to marginalise)
     cov = dict(pose_cov=np.zeros((N, 3, 3)), ray_cov=np.zeros((n_landmark, 2, 2)), info={})  # (no records: no blocks)
     if len(frame):
+        # a dict's "joint" entry rides along with the blocks; everything else about the blocks stays as covariance=True
+        cov_arg = (dict(landmarks="all", joint=covariance["joint"])
+                   if isinstance(covariance, dict) and "joint" in covariance else True)
         prec = ptzba.FP32 if precision == "fp32" else ptzba.FP64
         ls = ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
-                          covariance=True if covariance else None, pose_priors=priors, marginal_prior=marg,
+                          covariance=cov_arg if covariance else None, pose_priors=priors, marginal_prior=marg,
                           marginalize=leaving, ray_priors=rpriors or None)
         all_poses, landmarks, res = out[:3]
         if leaving is not None:
             marg_out = dict(marginal=out[-1]["marginal"].reindex(dict(enumerate(image_indices))), stats=out[-1]["stats"])
         if covariance:
             cov = dict(pose_cov=out[3][0], ray_cov=out[3][1], info=out[3][2])
+            if "joint" in out[3][2]:
+                cov["joint"] = out[3][2]["joint"]
         all_poses[0] = ref_pose
         if verbose:
             print(f"GPU LM: {res}")

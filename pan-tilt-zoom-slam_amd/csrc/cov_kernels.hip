@@ -101,7 +101,9 @@ __global__ __launch_bounds__(64) void k_cov_tile_inv(const double* __restrict__ 
   }
 }
 
-template <typename real>
+// JOINT (ptzba_covariance_joint's stage 1): one workgroup per block, so the workspace slice belongs to the block; every
+// Z_i stays, the block's first tile goes to a.block_t0 and no Gram matrix is formed (k_cov_cross forms them all)
+template <typename real, bool JOINT>
 __global__ __launch_bounds__(256) void k_cov_gram(CovArgs a) {
   __shared__ __attribute__((aligned(16))) double sA[NB][NB + 1];  // L_ik, then M_i, then G
   __shared__ __attribute__((aligned(16))) double sB[NB][NB + 1];  // Z_k, then the right-hand side, then Z_i
@@ -151,6 +153,7 @@ __global__ __launch_bounds__(256) void k_cov_gram(CovArgs a) {
       __syncthreads();
     }
     const int t0 = s_t0;
+    if (JOINT && tid == 0) a.block_t0[blk] = t0;
     v4f64 G = {0.0, 0.0, 0.0, 0.0};
     for (int i = t0; i < a.n_tiles; ++i) {
       v4f64 acc = {0.0, 0.0, 0.0, 0.0};
@@ -236,8 +239,9 @@ __global__ __launch_bounds__(256) void k_cov_gram(CovArgs a) {
       }
       __syncthreads();  // Z_i in LDS; its global copy is visible to this workgroup's later loads
       // ---- G += Z_i^T Z_i
-      cov_mma<true, false>(G, sB, sB);
+      if (!JOINT) cov_mma<true, false>(G, sB, sB);
     }
+    if (JOINT) continue;
     // ---- the diagonal blocks of G (lower triangle mirrored: symmetric bit for bit)
     __syncthreads();
     cov_acc_put(sA, G);
@@ -266,10 +270,80 @@ void launch_cov_tile_inv(const double* Ldiag, const uint8_t* pad, int n_aug, int
 
 template <typename real>
 void launch_cov_gram(const CovArgs& a, int n_groups, hipStream_t st) {
-  if (n_groups > 0) hipLaunchKernelGGL(k_cov_gram<real>, dim3(n_groups), dim3(256), 0, st, a);
+  if (n_groups > 0) hipLaunchKernelGGL((k_cov_gram<real, false>), dim3(n_groups), dim3(256), 0, st, a);
 }
 template void launch_cov_gram<float>(const CovArgs&, int, hipStream_t);
 template void launch_cov_gram<double>(const CovArgs&, int, hipStream_t);
+
+// G_ab = sum_{i >= max(t0_a, t0_b)} Z_{a,i}^T Z_{b,i} of the block pair (a, b) = (blockIdx.y, blockIdx.x), a >= b, from
+// the Z tiles stage 1 kept (tiles before a block's first tile hold stale memory and are never read), in ascending i:
+// deterministic, and for a == b the very sum k_cov_gram forms.  Epilogue: out[oi][oj] = out[oj][oi] = scale * (G_ij
+// (+ V_l^-1 on a landmark's own 2 x 2)), negated between a ray and a pose column (stage 1 builds +Y, the joint
+// covariance needs B = [E | -Y]); columns with col_out < 0 are skipped (the host zero-filled out).
+__global__ __launch_bounds__(256) void k_cov_cross(CovCrossArgs a) {
+  __shared__ __attribute__((aligned(16))) double sA[NB][NB + 1];  // Z_{a,i}, then G
+  __shared__ __attribute__((aligned(16))) double sB[NB][NB + 1];  // Z_{b,i}
+  __shared__ int s_oa[NB], s_ob[NB];
+  const int ba = blockIdx.y, bb = blockIdx.x, tid = threadIdx.x;
+  if (bb > ba) return;
+  if (tid < NB) s_oa[tid] = a.col_out[(int64_t)ba * NB + tid];
+  else if (tid < 2 * NB) s_ob[tid - NB] = a.col_out[(int64_t)bb * NB + tid - NB];
+  const int t0 = max(a.block_t0[ba], a.block_t0[bb]);
+  const double* __restrict__ Za = a.Z + (int64_t)ba * a.n_tiles * NB * NB;
+  const double* __restrict__ Zb = a.Z + (int64_t)bb * a.n_tiles * NB * NB;
+  double2 va[2], vb[2];
+  // as k_cov_gram: two pairs of adjacent elements per thread and tile, the next pair of tiles in flight in registers
+  auto fetch = [&](int i) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int64_t o = (int64_t)i * NB * NB + 2 * (tid + 256 * q);
+      va[q] = *reinterpret_cast<const double2*>(Za + o);
+      vb[q] = *reinterpret_cast<const double2*>(Zb + o);
+    }
+  };
+  v4f64 G = {0.0, 0.0, 0.0, 0.0};
+  if (t0 < a.n_tiles) fetch(t0);
+  for (int i = t0; i < a.n_tiles; ++i) {
+    __syncthreads();  // the previous product has read sA / sB
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int p = tid + 256 * q, r = p >> 4, c = 2 * (p & 15);
+      sA[r][c] = va[q].x; sA[r][c + 1] = va[q].y;
+      sB[r][c] = vb[q].x; sB[r][c + 1] = vb[q].y;
+    }
+    __syncthreads();
+    if (i + 1 < a.n_tiles) fetch(i + 1);
+    cov_mma<true, false>(G, sA, sB);
+  }
+  __syncthreads();
+  cov_acc_put(sA, G);
+  __syncthreads();
+  const double scale = a.scale_dev ? a.scale_dev[0] / a.scale_div : a.scale;
+  const bool ray_a = ba >= a.n_pose_blocks, ray_b = bb >= a.n_pose_blocks;
+  for (int e = tid; e < NB * NB; e += 256) {
+    const int i = e >> 5, j = e & 31;
+    const int oi = s_oa[i], oj = s_ob[j];
+    if (oi < 0 || oj < 0 || (ba == bb && j > i)) continue;  // (diagonal pairs: the lower triangle, mirrored)
+    double g = sA[i][j];
+    if (ba == bb && ray_a && (i >> 1) == (j >> 1)) {
+      const int l = a.lm_index[(int64_t)(ba - a.n_pose_blocks) * (NB / 2) + (i >> 1)];
+      g = a.lm_aux[(int64_t)l * 8 + (i & 1) + (j & 1)] + g;
+    }
+    double val = scale * g;
+    if (ray_a != ray_b) val = -val;
+    a.out[(int64_t)oi * a.n + oj] = val;
+    a.out[(int64_t)oj * a.n + oi] = val;
+  }
+}
+
+template <typename real>
+void launch_cov_joint(const CovArgs& z, const CovCrossArgs& x, hipStream_t st) {
+  if (x.n_blocks <= 0) return;
+  hipLaunchKernelGGL((k_cov_gram<real, true>), dim3(x.n_blocks), dim3(256), 0, st, z);
+  hipLaunchKernelGGL(k_cov_cross, dim3(x.n_blocks, x.n_blocks), dim3(256), 0, st, x);
+}
+template void launch_cov_joint<float>(const CovArgs&, const CovCrossArgs&, hipStream_t);
+template void launch_cov_joint<double>(const CovArgs&, const CovCrossArgs&, hipStream_t);
 
 // sum over the scalar residuals of w rho'(z) r^2 (z = (r / f_scale)^2; rho' = 1 for the linear loss and inside the
 // huber unit, 1 / sqrt(z) beyond): per-workgroup partials in a fixed order, summed by the last launch's one workgroup

@@ -389,12 +389,30 @@ struct CovArgs {
   const int4* lm_meta;         // [n_lm] {first frame, last frame, slot offset, 0}
   const int32_t* lm_seg_begin; // [n_lm + 1]
   double* ray_cov;             // [n_lm_sel][2][2]
+  int32_t* block_t0;           // joint stage 1 only: [blocks] the first tile each block wrote
+};
+// joint covariance, stage 2 (k_cov_cross): the Gram matrices of every block pair from the Z tiles stage 1 kept
+struct CovCrossArgs {
+  const double* Z;             // [n_blocks][n_tiles][32][32], pose blocks first
+  int n_tiles, n_blocks, n_pose_blocks;
+  const int32_t* block_t0;     // [n_blocks] first tile stage 1 wrote (the tiles before it are stale)
+  const int32_t* col_out;      // [n_blocks][32] output index of each column (-1: padding, fixed frame, no records)
+  const int32_t* lm_index;     // [16 per ray block] the chosen landmarks
+  const double* lm_aux;        // [n_lm][8] V^-1 (3) | ...
+  double scale;                // as CovArgs
+  const double* scale_dev;
+  double scale_div;
+  double* out;                 // [n][n], zero-filled by the host
+  int64_t n;
 };
 // min_piv [n_tiles]: the smallest pivot of each tile's system rows (NaN: not a number)
 void launch_cov_tile_inv(const double* Ldiag, const uint8_t* pad, int n_aug, int n_tiles, double* Minv,
                          double* min_piv, hipStream_t st);
 template <typename real>
 void launch_cov_gram(const CovArgs& a, int n_groups, hipStream_t st);
+// stage 1 (k_cov_gram keeping Z: z.work holds x.n_blocks slices, z.block_t0 == x.block_t0) and stage 2
+template <typename real>
+void launch_cov_joint(const CovArgs& z, const CovCrossArgs& x, hipStream_t st);
 // out[0] = sum over the scalar residuals of w rho' r^2 at the current tables (part: n_part doubles of scratch)
 template <typename real>
 void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,

@@ -75,6 +75,7 @@ class ptzba_cov_opts(Structure):
 
 
 COV_SCALE_UNIT, COV_SCALE_GIVEN, COV_SCALE_RESIDUAL = 0, 1, 2
+COV_JOINT_MAX_COLS = 2048  # PTZBA_COV_JOINT_MAX_COLS: columns of one ptzba_covariance_joint call
 
 
 class ptzba_pose_priors(Structure):
@@ -173,6 +174,7 @@ def lib():
         "ptzba_step": ([V, D], I),
         "ptzba_set_huber_curvature": ([V, D], I),
         "ptzba_covariance": ([V, POINTER(ptzba_cov_opts), V, V, I32, V, V], I),
+        "ptzba_covariance_joint": ([V, POINTER(ptzba_cov_opts), V, I32, V, I32, V, V], I),
         "ptzba_set_pose_priors": ([V, POINTER(ptzba_pose_priors)], I),
         "ptzba_pose_prior_info": ([V, V], I),
         "ptzba_set_ray_priors": ([V, POINTER(ptzba_ray_priors)], I),
@@ -288,7 +290,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_dist_rank_phases", "ptzba_dist_plan_export", "ptz_desc_put", "ptz_desc_drop", "ptz_match_knn2_sets",
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
     "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
-    "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info",
+    "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info", "ptzba_covariance_joint",
 ]
 
 
@@ -1495,13 +1497,8 @@ class BAHandle:
         """Host-driven LM: the huber curvature weight (units of rho' beyond the unit) of later linearisations."""
         _check(lib().ptzba_set_huber_curvature(self.h, float(hc)), "ptzba_set_huber_curvature")
 
-    def covariance(self, landmarks=None, scale=None, poses=True, _struct_size=None):
-        """Posterior covariance blocks at the current state (ptzba_covariance; a between-solves call): the diagonal
-        blocks of scale * (J^T diag(rho') J)^-1 over the free parameters.  landmarks: None (no rays), "all", or an
-        int array of landmark indices (duplicates allowed); scale: None (1), a positive float, or "residual"
-        (s^2 = sum(rho' r^2) / (2 R - n_free)); poses=False skips the pose blocks.  Returns (pose_cov [n_pose, 3, 3]
-        with the fixed frames' blocks zero, or None; ray_cov [k, 2, 2] or None; info dict: scale, min_pivot, n_free,
-        device_ms).  Raises PtzbaError when the undamped system is not positive definite."""
+    @staticmethod
+    def _cov_opts(scale, _struct_size=None):
         if scale is None:
             mode, sval = COV_SCALE_UNIT, 1.0
         elif isinstance(scale, str):
@@ -1510,7 +1507,16 @@ class BAHandle:
             mode, sval = COV_SCALE_RESIDUAL, 1.0
         else:
             mode, sval = COV_SCALE_GIVEN, float(scale)
-        opts = ptzba_cov_opts(ctypes.sizeof(ptzba_cov_opts) if _struct_size is None else int(_struct_size), mode, sval)
+        return ptzba_cov_opts(ctypes.sizeof(ptzba_cov_opts) if _struct_size is None else int(_struct_size), mode, sval)
+
+    def covariance(self, landmarks=None, scale=None, poses=True, _struct_size=None):
+        """Posterior covariance blocks at the current state (ptzba_covariance; a between-solves call): the diagonal
+        blocks of scale * (J^T diag(rho') J)^-1 over the free parameters.  landmarks: None (no rays), "all", or an
+        int array of landmark indices (duplicates allowed); scale: None (1), a positive float, or "residual"
+        (s^2 = sum(rho' r^2) / (2 R - n_free)); poses=False skips the pose blocks.  Returns (pose_cov [n_pose, 3, 3]
+        with the fixed frames' blocks zero, or None; ray_cov [k, 2, 2] or None; info dict: scale, min_pivot, n_free,
+        device_ms).  Raises PtzbaError when the undamped system is not positive definite."""
+        opts = self._cov_opts(scale, _struct_size)
         pose_cov = np.zeros((self.n_pose, 3, 3)) if poses else None
         idx = None
         if landmarks is None:
@@ -1528,6 +1534,32 @@ class BAHandle:
                                       _ptr(info)), "ptzba_covariance")
         return pose_cov, ray_cov, dict(scale=float(info[0]), min_pivot=float(info[1]), n_free=int(info[2]),
                                        device_ms=float(info[3]))
+
+    def covariance_joint(self, frames, landmarks=(), scale=None, _struct_size=None, _out=None):
+        """Dense joint posterior covariance of chosen parameters at the current state (ptzba_covariance_joint; a
+        between-solves call): the sub-matrix of scale * (J^T diag(rho') J + priors)^-1 over the given frames, (pan, tilt,
+        f) each in the given order, followed by the given landmarks, (theta, phi) each -- with one frame the EKF state
+        layout.  The diagonal blocks are covariance()'s; the cross blocks are the correlations it drops.  A fixed frame
+        and a landmark without records give zero rows and columns; a frame or landmark named twice is refused, as are
+        more than COV_JOINT_MAX_COLS columns.  scale as covariance().  Returns (cov [n, n], n = 3 len(frames) +
+        2 len(landmarks), symmetric bit for bit; info dict as covariance())."""
+        opts = self._cov_opts(scale, _struct_size)
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        lm = np.ascontiguousarray(landmarks, dtype=np.int32).reshape(-1)
+        n = 3 * len(fr) + 2 * len(lm)
+        cov = np.zeros((n, n)) if _out is None else _out
+        info = np.zeros(4)
+        _check(lib().ptzba_covariance_joint(self.h, ctypes.byref(opts), _ptr(fr) if len(fr) else c_void_p(0), len(fr),
+                                            _ptr(lm) if len(lm) else c_void_p(0), len(lm),
+                                            _ptr(cov) if cov.size else c_void_p(0), _ptr(info)),
+               "ptzba_covariance_joint")
+        return cov, dict(scale=float(info[0]), min_pivot=float(info[1]), n_free=int(info[2]), device_ms=float(info[3]))
+
+    def relative_pose_covariance(self, a, b, scale=None):
+        """Covariance [3, 3] of x_a - x_b, the relative pose (pan, tilt, f) of frames a and b: S_aa + S_bb - S_ab -
+        S_ba from one covariance_joint call.  A fixed frame contributes zeros, so against the gauge frame it is S_aa."""
+        C, _ = self.covariance_joint([int(a), int(b)], scale=scale)
+        return C[:3, :3] + C[3:, 3:] - C[:3, 3:] - C[3:, :3]
 
     def set_pose_priors(self, factors):
         """Gaussian pose priors (ptzba_set_pose_priors): factors = [(frames, mean, info), ...], see check_pose_priors.
@@ -1883,6 +1915,10 @@ class LMSolver:
         """BAHandle.covariance at the solver's solution (the handle's current state; call it after run())."""
         return self.h.covariance(landmarks=landmarks, scale=scale, poses=poses)
 
+    def covariance_joint(self, frames, landmarks=(), scale=None):
+        """BAHandle.covariance_joint at the solver's solution (the handle's current state; call it after run())."""
+        return self.h.covariance_joint(frames, landmarks, scale=scale)
+
     def run(self, iterations=None, check_termination=True):
         if self.device_loop and check_termination and not self.verbose:
             return self._run_device(iterations)
@@ -2081,7 +2117,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
           marginal_prior=None, marginalize=None, ray_priors=None, **lm_kw):
     """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
     BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
-    (pose_cov, ray_cov, info) at the solution.  keep_handle=True (default): one
+    (pose_cov, ray_cov, info) at the solution; an entry "joint": (frames, landmarks) in that dict adds
+    info["joint"], BAHandle.covariance_joint's matrix of them at the same scale.  keep_handle=True (default): one
     handle per device is kept between calls (a keyframe map solves on every new keyframe: creating and
     destroying a handle -- stream, pinned records, device buffers -- cost ~6 ms per call); set_problem replaces
     its problem and release_solve_handles() frees it.  keep_handle=False: a private handle, closed on return.
@@ -2108,7 +2145,12 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
 
     def finish(h, out):
         if covariance:
-            out = out + (h.covariance(**_cov_kwargs(covariance)),)
+            kw = _cov_kwargs(covariance)
+            joint = kw.pop("joint", None)
+            cov = h.covariance(**kw)
+            if joint is not None:  # (frames, landmarks): the dense joint matrix, added to the info dict
+                cov[2]["joint"] = h.covariance_joint(*joint, scale=kw.get("scale"))[0]
+            out = out + (cov,)
         if marginalize is not None:
             m, stats = h.marginal_prior(marginalize)
             out = out + (dict(marginal=m, stats=stats),)

@@ -5,6 +5,11 @@ blocks minus the call with none (same stream, the rest of the call identical), i
 tile product (L_ik Z_k, M_i B_i and Z_i^T Z_i) from the factor's tile pattern.  Writes profiles/cov_measure.json.
 
     python tools/cov_measure.py [out.json] [repeats]
+
+`joint` times ptzba_covariance_joint the same way at config 3 (fp32 + Huber) for three selections -- one frame + 500
+rays (1,003 columns), every free pose (1,497 columns), two frames -- next to ptzba_covariance's figures of the same
+run, and writes profiles/cov_joint_measure.json; `joint-fold` adds the two stages' kernel times from a
+rocprofv3 --kernel-trace CSV of a separate run (main_joint).
 """
 import json
 import os
@@ -111,7 +116,98 @@ def measure(cfg, precision, loss, repeats):
     return out
 
 
+def joint_shapes(p):
+    """The joint call's timed selections at a problem: one frame + 500 rays (the EKF layout at R = 500: the last frame
+    and the landmarks it sees first, filled up with others), every free pose, two frames."""
+    f = p.n_pose - 1
+    seen = np.unique(p.landmark[p.frame == f])
+    rest = np.setdiff1d(np.arange(p.n_landmark), seen)
+    rays = np.concatenate([seen, rest])[:500]
+    return [("one_frame_500_rays", [f], rays), ("all_free_poses", np.arange(1, p.n_pose), []),
+            ("two_frames", [1, f], [])]
+
+
+def measure_joint(repeats):
+    """ptzba_covariance_joint at config 3 (fp32 + Huber): HIP events around the whole call (its device_ms), 3 warm-up
+    calls, median of `repeats`; next to it ptzba_covariance's figures of the same run."""
+    p = synthetic.make_problem("config3", seed=0)
+    h = ptzba.BAHandle(0)
+    h.set_problem(p.n_pose, p.n_landmark, p.frame, p.landmark, p.xy, p.u, p.v, precision=ptzba.FP32,
+                  loss=ptzba.LOSS_HUBER, f_scale=1.0)
+    h.set_state(p.init_ptz, p.init_rays)
+    si = h.solver_info()
+
+    def timed(call, **kw):
+        for _ in range(3):
+            call(**kw)
+        return statistics.median(call(**kw)[-1]["device_ms"] for _ in range(repeats))
+
+    base = timed(h.covariance, landmarks=None, poses=False)
+    out = dict(config="config3", precision="fp32", loss="huber", n_pose=p.n_pose, n_landmark=p.n_landmark,
+               n_aug=si["n_aug"], row_tiles=(si["n_aug"] + NB - 1) // NB, repeats=repeats, cov_ms_no_blocks=base,
+               cov_ms_poses=timed(h.covariance, landmarks=None), cov_ms_poses_all_rays=timed(h.covariance, landmarks="all"),
+               joint=[])
+    for name, frames, rays in joint_shapes(p):
+        ms = timed(h.covariance_joint, frames=frames, landmarks=rays)
+        n_free = int(np.count_nonzero(np.asarray(frames) >= 1))
+        blocks = (n_free + POSE_F - 1) // POSE_F + (len(rays) + RAY_L - 1) // RAY_L
+        out["joint"].append(dict(shape=name, columns=3 * len(frames) + 2 * len(rays), column_blocks=blocks,
+                                 block_pairs=blocks * (blocks + 1) // 2,
+                                 z_workspace_bytes=blocks * out["row_tiles"] * NB * NB * 8,
+                                 joint_ms=ms, stages_ms=ms - base))
+    h.close()
+    return out
+
+
+def fold_kernel_trace(res, csv_path):
+    """Adds each shape's median kernel time of stage 1 (k_cov_gram keeping Z) and stage 2 (k_cov_cross) from a
+    rocprofv3 --kernel-trace CSV of a separate run of this tool; a shape's dispatches are told by their grid (one
+    workgroup of 256 per column block in x)."""
+    import csv
+    st1, st2 = {}, {}
+    with open(csv_path, newline="") as f:
+        for row in csv.DictReader(f):
+            name = row["Kernel_Name"]
+            gx = int(row.get("Grid_Size_X", row.get("Grid_Size", 0)))
+            us = (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) * 1e-3
+            if "k_cov_cross" in name:
+                st2.setdefault(gx // 256, []).append(us)
+            elif "k_cov_gram" in name and ("true" in name or "Lb1" in name):
+                st1.setdefault(gx // 256, []).append(us)
+    for s in res["joint"]:
+        b = s["column_blocks"]
+        if b in st1 and b in st2:
+            s["stage1_kernel_us"] = statistics.median(st1[b])
+            s["stage2_kernel_us"] = statistics.median(st2[b])
+            s["stage1_share"] = s["stage1_kernel_us"] / (s["stage1_kernel_us"] + s["stage2_kernel_us"])
+            s["kernel_trace_dispatches"] = len(st2[b])
+    return res
+
+
+def main_joint(argv):
+    """python tools/cov_measure.py joint [out.json] [repeats]: times the joint call, writes profiles/cov_joint_measure.json
+    python tools/cov_measure.py joint-fold out.json kernel_trace.csv: folds a kernel trace's stage times into it"""
+    default = os.path.join(ROOT, "profiles", "cov_joint_measure.json")
+    if argv[0] == "joint-fold":
+        with open(argv[1]) as f:
+            doc = json.load(f)
+        doc["config3"] = fold_kernel_trace(doc["config3"], argv[2])
+    else:
+        path = argv[1] if len(argv) > 1 else default
+        repeats = int(argv[2]) if len(argv) > 2 else 15
+        argv = [argv[0], path]
+        doc = dict(tool="tools/cov_measure.py joint", version=ptzba.lib().ptzba_version().decode(),
+                   config3=measure_joint(repeats))
+    print(json.dumps(doc), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(argv[1])), exist_ok=True)
+    with open(argv[1], "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] in ("joint", "joint-fold"):
+        return main_joint(sys.argv[1:])
     path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "cov_measure.json")
     repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 15
     res = []
