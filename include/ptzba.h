@@ -804,6 +804,16 @@ PTZBA_EXPORT int ptzekf_update(ptzekf_handle h, double u, double v, const double
  * the tile's splits; see ptzba_k2_tile_info); *n_out = the number of tiles.  out4 may be NULL with cap 0. */
 PTZBA_EXPORT int ptzba_schur_groups(ptzba_handle h, int32_t cap, int32_t* out4, int32_t* n_out);
 
+/* debug / test only: device pointers (read them, never write) and element counts of what the last solve of the reduced
+ * system left behind: [0] Ldiag, the 32 x 32 diagonal factor tiles, row-major, one per tile column (ld * 32 doubles;
+ * tile n_aug / 32 also holds the factor's augmented row), [1] Minv, their inverses (same shape; the tile of a column
+ * without pose rows is never written), [2] dpose, the pose step in the system order (ld doubles; rows from n_aug on
+ * are never written), [3] info, the factorisation's status (1 int: non-zero after a pivot that was not positive).  The
+ * off-diagonal factor tiles and the forward-substituted right-hand side (row n_aug) overwrite S in the exchange region
+ * (ptzba_exchange).  Stream-ordered like every buffer of the handle: ptzba_sync first.  The pointers hold until the
+ * next ptzba_set_problem (tests/test_gpu_k3_reference.py). */
+PTZBA_EXPORT int ptzba_solver_buffers(ptzba_handle h, void** ptrs4, int64_t* counts4);
+
 #ifdef __cplusplus
 }
 #endif

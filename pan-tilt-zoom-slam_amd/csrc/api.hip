@@ -2302,6 +2302,19 @@ int ptzba_solver_info(ptzba_handle h, int64_t* info8) {
   return 0;
 }
 
+int ptzba_solver_buffers(ptzba_handle h, void** ptrs, int64_t* counts) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!ptrs || !counts) return fail("bad arguments");
+  ptrs[0] = h->Ldiag.p;
+  ptrs[1] = h->Minv.p;
+  ptrs[2] = h->dpose.p;
+  ptrs[3] = h->info.p;
+  counts[0] = counts[1] = h->ld * CHOL_NB;
+  counts[2] = h->ld;
+  counts[3] = 1;
+  return 0;
+}
+
 int ptzba_residual(ptzba_handle h, const double* x_full, double* r_out) {
   if (!h || !h->have_problem) return fail("no problem set");
   HIPCHK(hipSetDevice(h->device));

@@ -165,6 +165,7 @@ def lib():
         "ptzba_build_info": ([V, V], I),
         "ptzba_schur_groups": ([V, I32, V, V], I),
         "ptzba_solver_info": ([V, V], I),
+        "ptzba_solver_buffers": ([V, V, V], I),
         "ptzba_residual": ([V, V, V], I),
         "ptzba_set_state": ([V, V, V], I),
         "ptzba_get_state": ([V, V, V], I),
@@ -291,6 +292,7 @@ EXPORTED_SYMBOLS = [
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
     "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
     "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info", "ptzba_covariance_joint",
+    "ptzba_solver_buffers",
 ]
 
 
@@ -1400,6 +1402,15 @@ class BAHandle:
                     ordering="nested" if (out[3] & 0xFF) != ORDER_NATURAL else "natural", nd_depth=int(out[3]) >> 8,
                     backsolve=("lookahead", "left-looking", "blocked")[int(out[4])], n_slot=int(out[5]), schur_items=int(out[6]),
                     pattern_tiles=int(out[7]))
+
+    def solver_buffers(self):
+        """Debug / test only (ptzba_solver_buffers): {name: (device pointer, element count)} of what the last solve of
+        the reduced system left behind -- Ldiag and Minv (ld * 32 doubles: one 32 x 32 tile per tile column), dpose (ld
+        doubles, system-row order) and info (1 int32).  Read-only; sync() first."""
+        ptrs = (c_void_p * 4)()
+        counts = np.zeros(4, np.int64)
+        _check(lib().ptzba_solver_buffers(self.h, ctypes.cast(ptrs, c_void_p), _ptr(counts)), "ptzba_solver_buffers")
+        return {k: (int(ptrs[i] or 0), int(counts[i])) for i, k in enumerate(("Ldiag", "Minv", "dpose", "info"))}
 
     def info(self):
         out = np.zeros(8, np.int64)

@@ -11,6 +11,7 @@ Task semantics (one int4 record, chol_kernels.hip):
 (Round 4's supercolumn tasks and their continuation records were removed in round 6 with chol_super.)
 """
 import numpy as np
+from scipy.linalg import solve_triangular
 
 NB = 32
 
@@ -106,6 +107,8 @@ def replay_levels(A, Ldiag, tasks, level_off, L0, L1):
             if i == k:
                 Ldiag[k] = Lkk
             else:
-                tile(i, k)[:] = np.linalg.solve(Lkk, Tt.T).T
+                # a triangular solve, as the kernel's sweep: componentwise stable under row scaling (numpy's general
+                # solve pivots through the graded systems of tests/k3_cases.py and loses their small rows)
+                tile(i, k)[:] = solve_triangular(Lkk, Tt.T, lower=True).T
         for (a, b), v in writes:
             tile(a, b)[:] = v

@@ -1,8 +1,9 @@
 """The factorisation plans libptzba builds (ptzba_plan_export, host only), replayed task by task on the CPU
 (tests/chol_plan_exec.py restates k_chol_step's tile tasks in numpy) on an SPD matrix with the reduced camera
 system's coupling structure, must reproduce numpy's Cholesky factor: the one- and two-level nested orders, the
-delayed trailing updates and their 2 x 2 trailing blocks.  Plan logic only: the device arithmetic is checked by
-the GPU tests (test_gpu_nested2.py, test_gpu_config4.py)."""
+delayed trailing updates and their 2 x 2 trailing blocks.  Plan logic only: the device arithmetic is pinned to a dense
+np.longdouble reference by test_gpu_k3_reference.py (which replays these plans through tests/k3_ref.py as its model), and
+one Gauss-Newton step is compared with a sparse solve in test_gpu_nested2.py and test_gpu_config4.py."""
 import os
 
 import numpy as np
