@@ -3,7 +3,7 @@
 // The reduced camera system S (SPD, block-banded: keyframes couple only to pan neighbours) replaces
 // scipy's dense SVD of the full Jacobian (trf.py:467 via bundle_adjustment.py:200).
 //
-// Storage: row-major [ld][ld] lower triangle in the solver's system order (api.hip: natural frame
+// Storage: row-major [ld][ld] lower triangle in the solver's system order (chol_plan.cpp: natural frame
 // order, or nested dissection [A | B reversed | C] with each part padded to whole 32-row tiles;
 // padding rows are identity).  Row n_aug holds b^T (augmented right-hand side) with a huge diagonal,
 // so row n_aug of the factor is y = L^-1 b: the forward substitution comes out of the factorisation.
@@ -582,8 +582,8 @@ struct CholTaskVal {
   const int4* rest;
   __device__ int4 get(int b) const { return b < CHOL_KT ? t[b] : rest[b - CHOL_KT]; }
 };
-// P2: plans with delayed trailing updates (a second pair of update panels per task, api.hip make_plan)
-// One factorisation task (api.hip make_plan: panel / trailing / inverse / trailing block) by the workgroup: the
+// P2: plans with delayed trailing updates (a second pair of update panels per task, chol_plan.cpp make_plan)
+// One factorisation task (chol_plan.cpp make_plan: panel / trailing / inverse / trailing block) by the workgroup: the
 // body of a level launch (k_chol_step).
 template <bool SG, bool P2, bool COH>
 __device__ __forceinline__ void chol_task(double* __restrict__ A, int64_t ld, const int4 tk, double* __restrict__ Ldiag,
@@ -614,7 +614,7 @@ __device__ __forceinline__ void chol_task(double* __restrict__ A, int64_t ld, co
   const int up0 = (tk.w & 0x3fff) - 1;
   const int up1 = ((tk.w >> 14) & 0x3fff) - 1;
   const int tmask = (tk.w >> 28) & 3;  // panel: which updates also apply to T
-  // delayed trailing updates (api.hip make_plan, period 2): a second pair of update panels rides in x
+  // delayed trailing updates (chol_plan.cpp make_plan, period 2): a second pair of update panels rides in x
   const int up2 = P2 ? (int)(((unsigned)tk.x >> 2) & 0x3fff) - 1 : -1;
   const int up3 = P2 ? (int)(((unsigned)tk.x >> 16) & 0x3fff) - 1 : -1;
   const int tmask2 = P2 ? (int)((unsigned)tk.x >> 30) : 0;
@@ -627,7 +627,7 @@ __device__ __forceinline__ void chol_task(double* __restrict__ A, int64_t ld, co
   CS_STAMP(0);
   CS_RT(0);
   if constexpr (P2 && !SG) {
-    if (type == 3) {  // 2 x 2 block of trailing tiles (api.hip make_plan): A_ij -= sum_p L_ip L_jp^T
+    if (type == 3) {  // 2 x 2 block of trailing tiles (chol_plan.cpp make_plan): A_ij -= sum_p L_ip L_jp^T
       chol_trail_block<COH>(A, ld, i, j, ((tk.w >> 28) & 3) | (((unsigned)tk.x >> 30) << 2), up0, up1, up2, up3, sA, sB);
       return;
     }
@@ -719,7 +719,7 @@ __device__ __forceinline__ void chol_task(double* __restrict__ A, int64_t ld, co
     blk_gemm_nt_sub<SG>(accD, sB[1], sB[1], s_sgp[1]);
     if (updT1) blk_gemm_nt_sub<SG>(accT, sA[1], sB[1], s_sgp[1]);
   }
-  if (pass2) {  // the delayed pair (api.hip make_plan) through the same panel buffers
+  if (pass2) {  // the delayed pair (chol_plan.cpp make_plan) through the same panel buffers
     if (any_up) __syncthreads();
     stage_pair(w3, w2, w5, w4, updT2 && up2 >= 0, up2 >= 0, updT3 && up3 >= 0, up3 >= 0);
     load_signs(up2, up3);
@@ -1099,7 +1099,7 @@ __global__ __launch_bounds__(64 * BSL_WAVES) void k_chol_backsolve_ll(
   }
 }
 
-// Blocked right-looking back substitution for large systems (api.hip make_bs_steps).  The left-looking
+// Blocked right-looking back substitution for large systems (chol_plan.cpp make_bs_steps).  The left-looking
 // form above streams the whole factor through ONE CU per chain (config 4: 224 MB of L tiles, 2.4 ms); here
 // every step is a launch of one workgroup per (block, target column t), so a step's L tiles are read by
 // ~60-120 CUs at once.  Workgroup = BSB_P waves, wave k owns block column c_k:

@@ -312,17 +312,17 @@ void launch_cholesky(double* A, int64_t ld, const int4* tasks, const int* task_o
                      int* info, hipStream_t st, double* sgn = nullptr, const int4* tasks_host = nullptr,
                      double* Minv = nullptr,  // Minv: target of type-2 tasks (diagonal tile inverses)
                      int first_level = 0,     // levels [first_level, n_launch)
-                     bool delayed = false);   // tasks carry a second pair of update panels (api.hip make_plan)
+                     bool delayed = false);   // tasks carry a second pair of update panels (chol_plan.cpp make_plan)
 
 // la_tasks: lookahead back substitution's [lookahead tile per position | task offsets per (chain, helper) |
-// tasks q << 16 | tile], built by the host plan (api.hip make_plan)
+// tasks q << 16 | tile], built by the host plan (chol_plan.cpp make_plan)
 constexpr int BS_HELPERS = 7;
 void launch_chol_backsolve(const double* L, int64_t ld, int n, int n_chain, int n_pos, const int* chain_off,
                            const int* chain_cols, const int* upd_off, const int* upd_tiles, int n_upd,
                            const int* la_tasks, int n_tasks, const double* Ldiag, double* Minv, double* xout,
                            const int* lo_off, const int* lo_tiles, hipStream_t st,
                            const int* tinv_list = nullptr, int n_tinv = 0);  // tinv_list: see k_tile_inv_list
-// blocked right-looking back substitution (large systems): one launch per step of api.hip make_bs_steps'
+// blocked right-looking back substitution (large systems): one launch per step of chol_plan.cpp make_bs_steps'
 // schedule (step_off_host: task offsets), r: scratch [ld]; BSB_P chain columns per block
 constexpr int BSB_P = 4;
 void launch_chol_backsolve_blk(const double* L, int64_t ld, int n, const int4* tasks, const int* step_off_host,
@@ -354,7 +354,7 @@ void launch_pack_region(double* S, int64_t ld, const int2* xt, int n_tiles, doub
                         double* buf, int mode, hipStream_t st);
 // task word w: bits 0-13 update panel p1 + 1, bits 14-27 p2 + 1 (0 = none), bits 28/29: p1/p2 also update T
 inline int chol_pack_updates(int p1, int p2, int tmask) { return (p1 + 1) | ((p2 + 1) << 14) | (tmask << 28); }
-// task word x: type (2 bits) + the second pair of update panels of a delayed-trailing plan (api.hip make_plan)
+// task word x: type (2 bits) + the second pair of update panels of a delayed-trailing plan (chol_plan.cpp make_plan)
 inline int chol_pack_type(int type, int p3, int p4, int tmask34) {
   return (int)((unsigned)type | ((unsigned)(p3 + 1) << 2) | ((unsigned)(p4 + 1) << 16) | ((unsigned)tmask34 << 30));
 }

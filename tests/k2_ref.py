@@ -169,7 +169,7 @@ def split16(x):
 
 
 def tile_plan(n_pose, frame, landmark, n_fixed=1):
-    """The tiles, lists and splits ptzba_set_problem builds (csrc/api.hip, "K2 structure"), restated: a list of
+    """The tiles, lists and splits ptzba_set_problem builds (csrc/problem_layout.cpp layout_k2), restated: a list of
     dict(f1b, chunk, lms (ascending), splits [(a0, a1)]).  A landmark enters chunk c > 0 when it sees a frame of the
     chunk; split weight = the smallest >= 256 whose item count fits the target (chunk-0 landmarks weigh 6, others 4)."""
     key = np.unique(landmark.astype(np.int64) * n_pose + frame.astype(np.int64))

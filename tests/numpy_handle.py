@@ -276,7 +276,7 @@ class NumpyPartHandle(NumpyBAHandle):
 
 
 class NumpyTreeHandle(NumpyPartHandle):
-    """The RANK-TREE protocol of libptzba (round 4: include/ptzba.h, api.hip make_plan_tree / solve_impl) in numpy.
+    """The RANK-TREE protocol of libptzba (round 4: include/ptzba.h, chol_plan.cpp make_plan_tree, api.hip solve_impl) in numpy.
     The rank's phases come from the library's own plan (ptzba.dist_rank_phases: its base -- own subtree or shared
     leaf -- then each ancestor separator up to the root, with each node's rank group).  Before a phase its columns
     (the phase block, the later phases' rows against it, b, g and diag U over its rows) are summed over the phase's

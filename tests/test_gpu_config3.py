@@ -201,7 +201,7 @@ def test_one_shot_solve_equals_lm_solver(gpu_available, config, precision, loss)
 
 def test_config3_two_level_dissection_matches_one_level(gpu_available, config3, monkeypatch):
     """The default order at config 3 is the two-level nested dissection (26 elimination levels, four
-    back-substitution chains: api.hip nested_order2); it must give the same LM iterates as the one-level order
+    back-substitution chains: chol_plan.cpp nested_order2); it must give the same LM iterates as the one-level order
     [A | B reversed | C] (PTZBA_ND_DEPTH=1): fp64 linear loss, 4 iterations, poses within 1e-9 deg / 1e-7 px,
     rays within 1e-9 deg, same iteration count and cost to 1e-12 relative."""
     import ptzba

@@ -1,4 +1,4 @@
-"""GPU parity of the two-level nested-dissection order (api.hip nested_order2: A1 | C1 | A2 | C2 | A3 | C3 | A4,
+"""GPU parity of the two-level nested-dissection order (chol_plan.cpp nested_order2: A1 | C1 | A2 | C2 | A3 | C3 | A4,
 four leaves factored side by side, four back-substitution chains over the separator tree) on a problem small
 enough for the oracle's sparse solve: one undamped Gauss-Newton step equals the sparse normal-equation
 solution of the reference residual (bundle_adjustment.py:25-106 via oracle/ptz_oracle.py) with every

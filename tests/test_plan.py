@@ -1,4 +1,4 @@
-"""Host-side checks of the reduced-system plan (api.hip choose_order_plan, through the host-only
+"""Host-side checks of the reduced-system plan (chol_plan.cpp choose_order_plan, through the host-only
 ptzba_plan_summary): which system order ptzba_set_problem picks for a coupling window, its elimination
 levels and back-substitution chains.  No device is needed.  The numeric equivalence of the orders (the
 same Gauss-Newton step and optimum under every order) is checked on the GPU (test_gpu_ba.py,
@@ -78,7 +78,7 @@ def test_config4_keeps_one_level_with_trailing_blocks(nd_env):
 
 def test_dist_form_choice_never_predicts_a_slowdown(nd_env):
     """Round 6: bench.py --gpus N picks the form of the sharded solve with the smaller predicted
-    trial (ptzba.choose_dist_form, api.hip ptzba_dist_form_estimate: slowest rank's factorisation estimate + its
+    trial (ptzba.choose_dist_form, plan_api.cpp ptzba_dist_form_estimate: slowest rank's factorisation estimate + its
     collectives as ring all-reduces).  Config 3's rank tree does not shorten the chain (its separators are dense ~110
     frames), so from 4 ranks on its extra exchanges lose to the replicated solve; config 4's tree factorisation is
     ~1.3x shorter than the whole system's and its exchanges are a fraction of the packed system, so it keeps the tree.

@@ -29,7 +29,7 @@ POSE_F, RAY_L = 10, 16          # frames / landmarks per right-hand-side block (
 
 
 def tile_pattern(pos, win, n_fixed, n_aug):
-    """Strictly lower tiles of the factor's pattern with fill (api.hip make_plan), rows < ceil(n_aug / 32)."""
+    """Strictly lower tiles of the factor's pattern with fill (chol_plan.cpp make_plan), rows < ceil(n_aug / 32)."""
     T = (n_aug + 1 + NB - 1) // NB
     nz = np.zeros((T, T), bool)
     n = len(pos)

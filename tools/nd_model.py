@@ -1,4 +1,4 @@
-"""Host model of the reduced-system plan (api.hip make_plan): tile pattern with symbolic fill, elimination
+"""Host model of the reduced-system plan (chol_plan.cpp make_plan): tile pattern with symbolic fill, elimination
 levels and back-substitution chain lengths for a given frame order.  Used to pick the nested-dissection
 depth without a GPU.
 
