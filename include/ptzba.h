@@ -45,8 +45,9 @@ typedef struct ptzba_ctx* ptzba_handle;
 /* precision: arithmetic/record type of the per-observation kernels.  The reduced camera system,
  * its factorisation and the parameter state are always fp64. */
 enum { PTZBA_FP64 = 0, PTZBA_FP32 = 1 };
-/* loss (scipy least_squares `loss=`): linear, or huber with f_scale */
-enum { PTZBA_LOSS_LINEAR = 0, PTZBA_LOSS_HUBER = 1 };
+/* loss (scipy least_squares `loss=`), per scalar residual r with z = (r / f_scale)^2, cost 1/2 f_scale^2 sum rho(z):
+ * linear rho = z; huber z | 2 sqrt(z) - 1; soft_l1 2 (sqrt(1 + z) - 1); cauchy ln(1 + z); arctan atan z */
+enum { PTZBA_LOSS_LINEAR = 0, PTZBA_LOSS_HUBER = 1, PTZBA_LOSS_SOFT_L1 = 2, PTZBA_LOSS_CAUCHY = 3, PTZBA_LOSS_ARCTAN = 4 };
 
 /* ordering of the reduced camera system: natural frame order, or one level of nested dissection
  * (left block | right block reversed | separator) when it shortens the factorisation's critical path */
@@ -54,8 +55,8 @@ enum { PTZBA_ORDER_NATURAL = 0, PTZBA_ORDER_NESTED = 1, PTZBA_ORDER_NESTED_FORCE
 
 typedef struct {
     int32_t precision;             /* PTZBA_FP64 | PTZBA_FP32 */
-    int32_t loss;                  /* PTZBA_LOSS_LINEAR | PTZBA_LOSS_HUBER */
-    double f_scale;                /* huber scale (scipy f_scale); ignored for linear */
+    int32_t loss;                  /* PTZBA_LOSS_LINEAR | _HUBER | _SOFT_L1 | _CAUCHY | _ARCTAN */
+    double f_scale;                /* the robust losses' scale (scipy f_scale, > 0); ignored for linear */
     int32_t n_fixed;               /* number of leading fixed (gauge) frames; the reference fixes frame 0 -> 1 */
     int32_t ordering;              /* PTZBA_ORDER_NATURAL | PTZBA_ORDER_NESTED */
     const int32_t* frame_win_hi;   /* optional [n_pose]: highest frame sharing a landmark with each frame,
@@ -226,11 +227,13 @@ typedef struct {
                                                  min_lambda (1e-12, the default) starts with Gauss-Newton steps, as
                                                  scipy's trf does while its step lies inside the trust region */
   int32_t max_iter, max_retries, gauss_newton; /* accepted iterations; rejections in a row; lambda0 = 0 GN */
-  /* huber loss only: the records' curvature weight beyond the unit is rho' (IRLS, a majoriser of the loss) until an
-   * accepted step was predicted to reduce the cost by less than curvature_switch of it; from then on huber_curvature * rho' (the
-   * loss's own Newton curvature is 0 there, scipy's robust scaling; floored), the current point re-linearised at
-   * once.  curvature_switch = 0 or huber_curvature = 1: IRLS throughout.  Defaults 0.1 / 0.25.  ABI (ptzba_version
-   * 0.2): these two fields were added after the 9-field struct of 0.1; they are read for the Huber loss only and
+  /* robust losses only (every loss but linear; the names are 0.2's, when Huber was the only one): a record's curvature
+   * weight is max(rho' + 2 z rho'', hc rho'), the loss's own Newton curvature (scipy's robust scaling) floored at hc
+   * rho'.  hc = 1 -- IRLS, a majoriser of the loss, since rho'' <= 0 -- until an accepted step was predicted to reduce
+   * the cost by less than curvature_switch of it; from then on hc = huber_curvature, the current point re-linearised at
+   * once.  For Huber that is rho' inside the unit and hc rho' beyond it (the Newton curvature is 1 | 0).
+   * curvature_switch = 0 or huber_curvature = 1: IRLS throughout.  Defaults 0.1 / 0.25.  ABI (ptzba_version
+   * 0.2): these two fields were added after the 9-field struct of 0.1; they are read for the robust losses only and
    * huber_curvature = 0 selects the default 0.1, so a caller that zero-fills them keeps IRLS throughout. */
   double huber_curvature, curvature_switch;
 } ptzba_lm_opts;
@@ -270,12 +273,14 @@ PTZBA_EXPORT int ptzba_solve(ptzba_handle h, double* ptz_inout, double* rays_ino
  * ptzba_save_state snapshot.  The state stays on the device (ptzba_get_state reads it).  Back-to-back solves
  * from C keep the restart's host reaction out of the device's timeline (bench.py's restart loop). */
 PTZBA_EXPORT int ptzba_solve_resident(ptzba_handle h, int restore, const ptzba_lm_opts* opts, ptzba_report* report);
-/* host-driven LM (ptzba_linearize / ptzba_step): the huber curvature weight (in (0, 1], units of rho' beyond the
- * unit) of the following linearisations; set_problem resets it to 1 (IRLS) */
+/* host-driven LM (ptzba_linearize / ptzba_step): the curvature floor hc (in (0, 1], units of rho'; see
+ * ptzba_lm_opts.huber_curvature) of the following linearisations, for every robust loss; set_problem resets it to 1
+ * (IRLS) */
 PTZBA_EXPORT int ptzba_set_huber_curvature(ptzba_handle h, double hc);
 /* Posterior covariance at the handle's current state (ptzba_version 0.3): the diagonal blocks of scale * H^-1, H the
  * undamped Gauss-Newton normal matrix J^T diag(rho') J over the free parameters [3 (n_pose - n_fixed) poses | rays]
- * (huber: the IRLS weights, whatever curvature the LM last used).  pose_cov [n_pose][3][3] (pan, tilt, f; the fixed
+ * (robust losses: the IRLS weights rho', whatever curvature the LM last used; scale_mode 2, the residual scale, is
+ * sum w rho' r^2 / (2 R - n_free) with the loss's rho').  pose_cov [n_pose][3][3] (pan, tilt, f; the fixed
  * frames' blocks all zero; may be NULL), ray_cov [n][2][2] of the landmarks lm_index[0 .. n_lm) (duplicates allowed;
  * n_lm = -1: every landmark in order, lm_index ignored; may be NULL when n_lm == 0; a landmark without records gets a
  * zero block).  info [4] (may be NULL): the scale used, the smallest pivot of the reduced system's Cholesky factor,
@@ -354,13 +359,13 @@ PTZBA_EXPORT int ptzba_pose_prior_info(ptzba_handle h, double* out4);
  * ptzba_marginal_prior turns the records named by drop_mask (one byte per record, ptzba_set_problem's record order;
  * non-zero = dropped) and the leaving frames E = drop_frames into one dense information-form factor over the frame
  * set K: the free frames outside E that carry a dropped record or are named by an absorbed factor, ascending.
- * Everything is linearised at the handle's current state x (Huber rows scaled by sqrt(rho'), curvature 1).  The
+ * Everything is linearised at the handle's current state x (a robust loss's rows scaled by sqrt(rho'), curvature 1).  The
  * landmarks of the dropped records are treated as independent copies, linearised at the current ray and eliminated
  * with the dropped records only, so no kept observation is counted twice:
  *     S_D = U_D - sum_l W_l V_l^-1 W_l^T,   b_D = g_p - sum_l W_l V_l^-1 g_l      (dropped records only)
  *     A = S_D(K u E) + sum_absorbed Lambda_k,   a = b_D(K u E) + sum_absorbed (Lambda_k e_k [+ eta_k])
  *     info = A_KK - A_KE A_EE^-1 A_EK,   grad = a_K - A_KE A_EE^-1 a_E,   lin = x_K
- *     offset = 1/2 sum_D rho(r^2) + the absorbed factors' cost at x
+ *     offset = 1/2 f_scale^2 sum_D rho((r / f_scale)^2) + the absorbed factors' cost at x
  * and the factor stands for q(x) = offset + grad^T d + 1/2 d^T info d, d = x_K - lin.  A factor is absorbed (whole;
  * its other frames join K) when it names a free frame of E: pose-prior factors and the handle's marginal factor.
  * Fixed frames of E (< n_fixed) have no columns.  info is positive semi-definite and generally singular.
@@ -573,7 +578,7 @@ PTZBA_EXPORT int ptz_h_jacobian(int device, int64_t n, double u, double v, doubl
  * (2 ftol, 3 xtol, 0 max_iter, -1 no decrease).  Any output pointer may be NULL. */
 typedef struct {
     int32_t max_iter;  /* default 100 */
-    int32_t loss;      /* PTZBA_LOSS_LINEAR | PTZBA_LOSS_HUBER */
+    int32_t loss;      /* PTZBA_LOSS_* (the robust ones with IRLS weights; they need f_scale > 0) */
     double ftol;       /* the reference's 1e-4 */
     double xtol;       /* scipy default 1e-8 */
     double f_scale;

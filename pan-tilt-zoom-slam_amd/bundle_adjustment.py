@@ -17,7 +17,7 @@ Steps 2, 3 and 5 run on correspondence.MatchGraph (native builder, SURVEY 8f-2);
 correspondence.CorrespondenceCache as `correspondences=` to skip re-detection/re-matching.
 
 Extra keyword arguments (all optional) select the numerics: precision ('fp64' default, 'fp32'),
-loss ('linear' as the reference, or 'huber'), f_scale, ftol/xtol/max_iter, device.
+loss ('linear' as the reference, or scipy's 'huber', 'soft_l1', 'cauchy', 'arctan'), f_scale, ftol/xtol/max_iter, device.
 `_compute_residual` keeps the reference signature and returns the identical residual vector
 (computed by libptzba, record order == the reference's loop order).
 """
@@ -130,7 +130,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
     (row l belongs to landmarks[l]) and `info`: the posterior covariance blocks (J^T J)^-1 at the returned solution
-    (ptzba.BAHandle.covariance; with loss='huber' the IRLS-weighted normal matrix).  covariance={"joint": (frames,
+    (ptzba.BAHandle.covariance; with a robust loss the IRLS-weighted normal matrix).  covariance={"joint": (frames,
     landmarks)} -- positions in `images` and landmark ids -- adds `joint` (also `info["joint"]`), the dense joint covariance of those
     parameters (ptzba.BAHandle.covariance_joint: frames first, 3 each, then landmarks, 2 each).
     pose_priors (keyword only; off: the call and its outputs are unchanged): Gaussian pose prior factors
@@ -155,6 +155,8 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
+    if not isinstance(loss, str) or loss not in ptzba.LOSS_IDS:  # (before any image work)
+        raise ValueError(f"unknown loss {loss!r}: one of {sorted(ptzba.LOSS_IDS)}")
     N = len(images)
     assert N >= 1
     assert len(image_indices) == N
@@ -270,7 +272,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         cov_arg = (dict(landmarks="all", joint=covariance["joint"])
                    if isinstance(covariance, dict) and "joint" in covariance else True)
         prec = ptzba.FP32 if precision == "fp32" else ptzba.FP64
-        ls = ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR
+        ls = ptzba.LOSS_IDS[loss]
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
                           covariance=cov_arg if covariance else None, pose_priors=priors, marginal_prior=marg,

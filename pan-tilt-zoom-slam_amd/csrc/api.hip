@@ -17,6 +17,7 @@
 #include "ba_ctx.h"
 #include "chol_plan.h"
 #include "problem_layout.h"
+#include "robust_loss.h"
 
 using namespace ptzba;
 
@@ -90,16 +91,19 @@ hipEvent_t ptzba::tm_k1_event(ptzba_ctx* h, int which) {
 
 const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.2 (round 6): ptzba_lm_opts carries huber_curvature / curvature_switch (11 fields; 0.1 had 9).  They are read
-// for the Huber loss only, and huber_curvature 0 means the default 0.1, so a zero-filled tail keeps 0.1's behaviour.
+// for the robust losses only (0.9: every one, Huber alone before), and huber_curvature 0 means the default 0.1, so a zero-filled tail keeps 0.1's behaviour.
 // 0.3: ptzba_covariance / ptzba_cov_opts (sized by its struct_size field); ptzba_lm_opts as in 0.2.
 // 0.4: ptzba_set_pose_priors / ptzba_pose_priors (sized by struct_size) / ptzba_pose_prior_info.
 // 0.5: ptzba_marginal_prior / ptzba_set_marginal_prior / ptzba_marginal_prior_info (structs sized by struct_size).
 // 0.6: ptzba_set_ray_priors / ptzba_ray_priors (sized by struct_size) / ptzba_ray_prior_info.
 // 0.7: ptzba_build_info (read-only counters of the builds' launch path).
 // 0.8: ptzba_covariance_joint (ptzba_cov_opts as 0.3).
+// 0.9: PTZBA_LOSS_SOFT_L1 / _CAUCHY / _ARCTAN (no struct changes; huber_curvature / curvature_switch are read for
+// every robust loss).
 const char* ptzba_version(void) {
-  return "ptzba 0.8 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
-         "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors as 0.6; ptzba_build_info as 0.7; ptzba_covariance_joint)";
+  return "ptzba 0.9 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
+         "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors as 0.6; ptzba_build_info as 0.7; ptzba_covariance_joint "
+         "as ptzba 0.8; losses soft_l1 / cauchy / arctan)";
 }
 
 ptzba_handle ptzba_new(int device) {
@@ -525,9 +529,9 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   ptzba_problem_opts o{PTZBA_FP64, PTZBA_LOSS_LINEAR, 1.0, 1, PTZBA_ORDER_NESTED, nullptr};
   if (opts) o = *opts;
   if (o.precision != PTZBA_FP64 && o.precision != PTZBA_FP32) return fail("bad precision %d", o.precision);
-  if (o.loss != PTZBA_LOSS_LINEAR && o.loss != PTZBA_LOSS_HUBER) return fail("bad loss %d", o.loss);
+  if (!loss_is_known(o.loss)) return fail("bad loss %d", o.loss);
   if (o.n_fixed < 0 || o.n_fixed > n_pose) return fail("bad n_fixed %d", o.n_fixed);
-  if (o.loss == PTZBA_LOSS_HUBER && !(o.f_scale > 0)) return fail("huber needs f_scale > 0");
+  if (o.loss != PTZBA_LOSS_LINEAR && !(o.f_scale > 0)) return fail("a robust loss needs f_scale > 0");
   if (o.ordering < PTZBA_ORDER_NATURAL || o.ordering > PTZBA_ORDER_NESTED_FORCE) return fail("bad ordering %d", o.ordering);
   if (o.frame_win_hi)
     for (int f = 0; f < n_pose; ++f)
@@ -1313,12 +1317,13 @@ int ptzba_lm_init(ptzba_handle h, const ptzba_lm_opts* o) {
   if (!(o->lambda0 >= 0) || !(o->min_lambda > 0) || !(o->max_lambda > 0) || o->max_iter < 0 || o->max_retries < 1)
     return fail("bad LM options");
   HIPCHK(hipSetDevice(h->device));
-  // the two curvature fields (added in version 5 of the options struct) matter for the Huber loss only; a caller that
+  // the two curvature fields (added in version 5 of the options struct) matter for the robust losses only; a caller that
   // zero-fills them gets the default curvature (0.1) and no switch (curvature_switch 0)
   const double hcv = o->huber_curvature == 0.0 ? 0.1 : o->huber_curvature;
-  if (h->loss == PTZBA_LOSS_HUBER && (!(hcv > 0.0 && hcv <= 1.0) || !(o->curvature_switch >= 0.0)))
+  const bool robust = h->loss != PTZBA_LOSS_LINEAR;
+  if (robust && (!(hcv > 0.0 && hcv <= 1.0) || !(o->curvature_switch >= 0.0)))
     return fail("bad LM options (huber_curvature in (0, 1], curvature_switch >= 0)");
-  const bool sw = h->loss == PTZBA_LOSS_HUBER && o->curvature_switch > 0.0 && hcv < 1.0;
+  const bool sw = robust && o->curvature_switch > 0.0 && hcv < 1.0;
   LMParams p{o->ftol, o->xtol, o->gtol, o->lambda0, o->min_lambda, o->max_lambda,
              sw ? hcv : 1.0, sw ? o->curvature_switch : 0.0, o->max_iter, o->max_retries,
              o->gauss_newton ? 1 : 0, 0};

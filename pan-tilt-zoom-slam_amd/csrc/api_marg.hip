@@ -283,7 +283,7 @@ int ptzba_marginal_prior(ptzba_handle h, const ptzba_marg_opts* o, const int32_t
       upload(g.pat, pat, h->st) || upload(g.fac, fac, h->st) || upload(g.fac_frames, fac_frames, h->st) ||
       upload(g.fac_loc, fac_loc, h->st))
     return -1;
-  // the caller's run state this call borrows: huber curvature, damping, timing groups, K1's weight array
+  // the caller's run state this call borrows: the robust losses' ("huber") curvature, damping, timing groups, K1's weight array
   struct Restore {
     ptzba_ctx* h;
     double hcurv, lambda;

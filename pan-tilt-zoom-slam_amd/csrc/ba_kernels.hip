@@ -27,6 +27,9 @@
 #include <hip/hip_ext.h>
 
 #include "ptzba_kernels.h"
+#include "robust_loss.h"
+
+#include <type_traits>
 
 namespace ptzba {
 
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
         wx = wt; wy = wt;
         hx = wt; hy = wt;
         c = wt * (rx * rx + ry * ry);
-      } else {
+      } else if constexpr (LOSS == 1) {
         real zx = rx * rx * ifs2, zy = ry * ry * ifs2;
         bool ix = zx <= (real)1, iy = zy <= (real)1;
         real sqx, sqy;
@@ -340,6 +343,14 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
         c = wt * fs2 * ((ix ? zx : (real)2 * sqx - (real)1) + (iy ? zy : (real)2 * sqy - (real)1));
         hx = ix ? wx : wx * hc;
         hy = iy ? wy : wy * hc;
+      } else {  // soft_l1 / cauchy / arctan (robust_loss.h): w1 = rho', w2 = max(rho' + 2 z rho'', hc rho')
+        real rhx, rhy, w1x, w1y, wnx, wny;
+        robust_eval<LOSS, real>(rx * rx * ifs2, rhx, w1x, wnx);
+        robust_eval<LOSS, real>(ry * ry * ifs2, rhy, w1y, wny);
+        wx = wt * w1x; wy = wt * w1y;
+        hx = wt * robust_curv(w1x, wnx, hc);
+        hy = wt * robust_curv(w1y, wny, hc);
+        c = wt * fs2 * (rhx + rhy);
       }
       cb += c;
       // runs merged forward as the records are formed (round 6: only the open run is live, not all RPL records'
@@ -513,12 +524,18 @@ void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0
     else hipLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, a);
   };
   const bool wt = a.rec_w != nullptr;
-  if (ftl) {
-    if (loss == 0) wt ? go(k_linearize<real, 0, true, true>) : go(k_linearize<real, 0, true, false>);
-    else wt ? go(k_linearize<real, 1, true, true>) : go(k_linearize<real, 1, true, false>);
-  } else {
-    if (loss == 0) wt ? go(k_linearize<real, 0, false, true>) : go(k_linearize<real, 0, false, false>);
-    else wt ? go(k_linearize<real, 1, false, true>) : go(k_linearize<real, 1, false, false>);
+  // one instantiation per loss (the template value is the PTZBA_LOSS_* id), frame-table path and weight form
+  auto pick = [&](auto loss_c) {
+    constexpr int L = decltype(loss_c)::value;
+    if (ftl) wt ? go(k_linearize<real, L, true, true>) : go(k_linearize<real, L, true, false>);
+    else wt ? go(k_linearize<real, L, false, true>) : go(k_linearize<real, L, false, false>);
+  };
+  switch (loss) {
+    case PTZBA_LOSS_LINEAR: pick(std::integral_constant<int, PTZBA_LOSS_LINEAR>{}); break;
+    case PTZBA_LOSS_HUBER: pick(std::integral_constant<int, PTZBA_LOSS_HUBER>{}); break;
+    case PTZBA_LOSS_SOFT_L1: pick(std::integral_constant<int, PTZBA_LOSS_SOFT_L1>{}); break;
+    case PTZBA_LOSS_CAUCHY: pick(std::integral_constant<int, PTZBA_LOSS_CAUCHY>{}); break;
+    default: pick(std::integral_constant<int, PTZBA_LOSS_ARCTAN>{}); break;  // (ptzba_set_problem refuses other ids)
   }
 }
 

@@ -19,6 +19,7 @@
 // memory) are never visited: the walk follows a row CSR of the pattern built by the host.
 #include "ptzba_common.h"
 #include "ptzba_kernels.h"
+#include "robust_loss.h"
 
 namespace ptzba {
 
@@ -346,7 +347,8 @@ template void launch_cov_joint<float>(const CovArgs&, const CovCrossArgs&, hipSt
 template void launch_cov_joint<double>(const CovArgs&, const CovCrossArgs&, hipStream_t);
 
 // sum over the scalar residuals of w rho'(z) r^2 (z = (r / f_scale)^2; rho' = 1 for the linear loss and inside the
-// huber unit, 1 / sqrt(z) beyond): per-workgroup partials in a fixed order, summed by the last launch's one workgroup
+// huber unit, 1 / sqrt(z) beyond, robust_loss.h's for the smooth losses; `loss` a PTZBA_LOSS_* id): per-workgroup
+// partials in a fixed order, summed by the last launch's one workgroup
 template <typename real>
 __global__ __launch_bounds__(256) void k_cov_resid_part(const int32_t* __restrict__ rec_seg,
                                                         const int32_t* __restrict__ seg_frame,
@@ -355,7 +357,7 @@ __global__ __launch_bounds__(256) void k_cov_resid_part(const int32_t* __restric
                                                         const real* __restrict__ rec_xy, const real* __restrict__ rec_w,
                                                         const FrameTab<double>* __restrict__ ft64,
                                                         const RayTab<double>* __restrict__ rt64, double u, double v,
-                                                        int64_t n_rec, int huber, double inv_fs2,
+                                                        int64_t n_rec, int loss, double inv_fs2,
                                                         double* __restrict__ part) {
   __shared__ double red[256 / WAVE];
   double s = 0.0;
@@ -366,10 +368,16 @@ __global__ __launch_bounds__(256) void k_cov_resid_part(const int32_t* __restric
     const double2 bs = seg_base[sg];
     const double ex = (double)((real)(x - bs.x) - rec_xy[2 * r]), ey = (double)((real)(y - bs.y) - rec_xy[2 * r + 1]);
     double qx = ex * ex, qy = ey * ey;
-    if (huber) {
+    if (loss == PTZBA_LOSS_HUBER) {
       const double zx = qx * inv_fs2, zy = qy * inv_fs2;
       if (zx > 1.0) qx /= sqrt(zx);
       if (zy > 1.0) qy /= sqrt(zy);
+    } else if (loss != PTZBA_LOSS_LINEAR) {
+      double rho, w1x, w1y, wn;
+      robust_eval_id(loss, qx * inv_fs2, rho, w1x, wn);
+      robust_eval_id(loss, qy * inv_fs2, rho, w1y, wn);
+      qx *= w1x;
+      qy *= w1y;
     }
     s += (rec_w ? (double)rec_w[r] : 1.0) * (qx + qy);
   }
@@ -392,10 +400,10 @@ __global__ void k_cov_resid_sum(const double* __restrict__ part, int n, double* 
 template <typename real>
 void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                       const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
-                      int64_t n_rec, int huber, double f_scale, double* part, int n_part, double* out, hipStream_t st) {
+                      int64_t n_rec, int loss, double f_scale, double* part, int n_part, double* out, hipStream_t st) {
   hipLaunchKernelGGL(k_cov_resid_part<real>, dim3(n_part), dim3(256), 0, st, rec_seg, seg_frame, seg_lm, seg_base,
                      (const real*)rec_xy, (const real*)rec_w, (const FrameTab<double>*)ft64,
-                     (const RayTab<double>*)rt64, u, v, n_rec, huber, 1.0 / (f_scale * f_scale), part);
+                     (const RayTab<double>*)rt64, u, v, n_rec, loss, 1.0 / (f_scale * f_scale), part);
   hipLaunchKernelGGL(k_cov_resid_sum, dim3(1), dim3(64), 0, st, part, n_part, out);
 }
 template void launch_cov_resid<float>(const int32_t*, const int32_t*, const int32_t*, const double2*, const void*,

@@ -7,6 +7,7 @@
 
 #include "../../include/ptzba.h"
 #include "ptzba_common.h"
+#include "robust_loss.h"
 
 namespace ptzba {
 
@@ -70,6 +71,11 @@ __device__ void rf_eval(const RefineArgs& a, int h, const double p[3], double (&
     double wx = 1, wy = 1, c2;
     if (a.loss == PTZBA_LOSS_LINEAR) {
       c2 = rx * rx + ry * ry;
+    } else if (a.loss != PTZBA_LOSS_HUBER) {  // soft_l1 / cauchy / arctan (robust_loss.h), IRLS weight rho'(z)
+      double px, py, nx, ny;
+      robust_eval_id(a.loss, rx * rx * a.inv_fs2, px, wx, nx);
+      robust_eval_id(a.loss, ry * ry * a.inv_fs2, py, wy, ny);
+      c2 = a.fs2 * (px + py);
     } else {  // scipy 'huber' as in K1: rho(z) = z | 2 sqrt(z) - 1, IRLS weight rho'(z)
       const double zx = rx * rx * a.inv_fs2, zy = ry * ry * a.inv_fs2;
       const double sx = sqrt(zx), sy = sqrt(zy);

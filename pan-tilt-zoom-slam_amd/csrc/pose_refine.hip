@@ -53,7 +53,8 @@ int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, int64_t n_cor
   ptz_refine_opts o{100, PTZBA_LOSS_LINEAR, 1e-4, 1e-8, 1.0};
   if (opts) o = *opts;
   if (o.max_iter < 0 || !(o.ftol >= 0) || !(o.xtol >= 0)) return fail("bad options");
-  if (o.loss == PTZBA_LOSS_HUBER && !(o.f_scale > 0)) return fail("huber needs f_scale > 0");
+  if (!loss_is_known(o.loss)) return fail("bad loss %d", o.loss);
+  if (o.loss != PTZBA_LOSS_LINEAR && !(o.f_scale > 0)) return fail("a robust loss needs f_scale > 0");
   int64_t n_sub = 0;
   if (subset_offsets) {
     if (subset_offsets[0] != 0) return fail("subset_offsets[0] must be 0");

@@ -91,7 +91,8 @@ struct LinArgs {
   const void* rt64;              // RayTab<double>[n_lm]
   const double2* seg_base;       // [n_seg] base observation; records hold obs - base (real)
   double u, v, fs2, inv_fs2;
-  double hcurv;                  // huber: curvature weight beyond the unit = hcurv * rho' (1: IRLS)
+  double hcurv;                  // robust losses: the curvature weight's floor in units of rho' (huber: the weight
+                                 // beyond the unit; robust_loss.h: max(rho' + 2 z rho'', hcurv rho')); 1: IRLS
   const double* hcurv_dev;       // device-driven LM: the curvature weight from LMDev::hc instead (nullptr: hcurv)
   const int* run_if;             // nullptr, or: the launch exits at once unless *run_if != 0 (re-linearisation)
   void* ug_slot;                 // [n_slot][UG_STRIDE] real: U (6) | g_pose (3) (dense slots)
@@ -417,7 +418,7 @@ void launch_cov_joint(const CovArgs& z, const CovCrossArgs& x, hipStream_t st);
 template <typename real>
 void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                       const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
-                      int64_t n_rec, int huber, double f_scale, double* part, int n_part, double* out, hipStream_t st);
+                      int64_t n_rec, int loss, double f_scale, double* part, int n_part, double* out, hipStream_t st);
 
 // Gaussian pose priors (prior_kernels.hip; ptzba_set_pose_priors): factor k names G_k free frames, a mean and a
 // symmetric information matrix Lambda_k over their 3 G_k pose parameters; cost += 1/2 sum_k e_k^T Lambda_k e_k,

@@ -27,13 +27,26 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PTZBA_LIB", os.path.join(_HERE, "libptzba.so"))
 
 FP64, FP32 = 0, 1
-LOSS_LINEAR, LOSS_HUBER = 0, 1
+LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_ARCTAN = 0, 1, 2, 3, 4
+# scipy least_squares' loss names -> PTZBA_LOSS_* ids (include/ptzba.h)
+LOSS_IDS = {"linear": LOSS_LINEAR, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY,
+            "arctan": LOSS_ARCTAN}
 NSCALARS = 8
 
 _lib = None
 
 
 ORDER_NATURAL, ORDER_NESTED, ORDER_NESTED_FORCE = 0, 1, 2
+
+
+def loss_id(loss):
+    """A loss given by scipy's name or by its PTZBA_LOSS_* id -> the id.  An unknown name raises ValueError (an
+    unknown id is refused by the library)."""
+    if isinstance(loss, str):
+        if loss not in LOSS_IDS:
+            raise ValueError(f"unknown loss {loss!r}: one of {sorted(LOSS_IDS)}")
+        return LOSS_IDS[loss]
+    return int(loss)
 
 
 class ptz_refine_opts(Structure):
@@ -55,7 +68,7 @@ class ptzba_lm_opts(Structure):
 # LM defaults (include/ptzba.h ptzba_lm_opts).  lambda0 = min_lambda: Gauss-Newton steps from the start, as scipy's trf
 # takes them while the step lies inside its trust region (bundle_adjustment.py:200-202 -> trf.py); a Marquardt start
 # (1e-4, rounds 1-4) damps the frame chain's low-curvature modes and stops at ftol=1e-4 ~5e-4 deg short of the optimum
-# at config 3 (profiles/r05a_ftol_study.jsonl).  Huber: IRLS curvature until an accepted step is predicted to reduce the
+# at config 3 (profiles/r05a_ftol_study.jsonl).  Robust losses (Huber's names): IRLS curvature until an accepted step is predicted to reduce the
 # cost by less than CURVATURE_SWITCH of it, then HUBER_CURVATURE * rho' beyond the unit (profiles/r05c_switch.jsonl)
 LAMBDA0 = 1e-12
 MIN_LAMBDA = 1e-12
@@ -603,7 +616,8 @@ def refine_poses(u, v, init_ptz, rays, points, subsets=None, ftol=1e-4, xtol=1e-
                  f_scale=1.0, device=0):
     """Pose-only LM with the rays fixed (relocalization.py:22-40, 186), batched over hypotheses.
     init_ptz [n_hyp, 3]; rays / points [n, 2]; subsets: optional list of index arrays (one per
-    hypothesis).  Returns (ptz [n_hyp, 3], cost [n_hyp], iterations [n_hyp], status [n_hyp])."""
+    hypothesis).  loss: a LOSS_* id or scipy's name (IRLS weights for the robust ones).
+    Returns (ptz [n_hyp, 3], cost [n_hyp], iterations [n_hyp], status [n_hyp])."""
     ptz = _f64(init_ptz).reshape(-1, 3).copy()
     rays = _f64(rays).reshape(-1, 2)
     points = _f64(points).reshape(-1, 2)
@@ -621,7 +635,7 @@ def refine_poses(u, v, init_ptz, rays, points, subsets=None, ftol=1e-4, xtol=1e-
     cost = np.zeros(n_hyp)
     its = np.zeros(n_hyp, np.int32)
     st = np.zeros(n_hyp, np.int32)
-    opts = ptz_refine_opts(int(max_iter), int(loss), float(ftol), float(xtol), float(f_scale))
+    opts = ptz_refine_opts(int(max_iter), loss_id(loss), float(ftol), float(xtol), float(f_scale))
     _check(lib().ptz_refine_poses(int(device), n_hyp, _ptr(ptz), len(rays), _ptr(rays), _ptr(points), float(u),
                                   float(v), _ptr(off), _ptr(idx), ctypes.byref(opts), _ptr(cost), _ptr(its), _ptr(st)),
            "ptz_refine_poses")
@@ -1310,7 +1324,8 @@ class BAHandle:
         every rank of a sharded solve (frame_coupling_window() of the full record set).  dist_world >= 2: this
         rank's share of a sharded solve, its landmarks chosen by partition_landmarks (part-owned solve when the
         frame chain splits, else replicated); the exchanges then run inside the library (attach_comm /
-        set_exchange_hook)."""
+        set_exchange_hook).  loss: a LOSS_* id or scipy's name (LOSS_IDS); an unknown name raises ValueError."""
+        loss = loss_id(loss)
         frame = np.ascontiguousarray(frame, dtype=np.int32)
         landmark = np.ascontiguousarray(landmark, dtype=np.int32)
         xy = _f64(xy, (-1, 2))
@@ -1985,11 +2000,12 @@ class LMSolver:
     def _run_host(self, iterations=None, check_termination=True):
         h = self.h
         t0 = time.perf_counter()
-        # huber curvature switch (ptzba_lm_opts; the device loop's k_lm_decide rule): IRLS until an accepted step
+        # curvature switch of the robust losses (ptzba_lm_opts; the device loop's k_lm_decide rule): IRLS until an accepted step
         # is predicted to reduce the cost by less than curvature_switch of it, then huber_curvature, the current point re-linearised
         # every host run starts from IRLS (curvature 1), switch or not: a previous run on this handle may have left its
         # reduced curvature behind (ptzba_set_problem / ptzba_lm_start reset it, a host run did not before round 6)
-        huber = getattr(h, "loss", LOSS_LINEAR) == LOSS_HUBER and hasattr(h, "set_huber_curvature")
+        # (`huber`: any robust loss)
+        huber = getattr(h, "loss", LOSS_LINEAR) != LOSS_LINEAR and hasattr(h, "set_huber_curvature")
         switch = huber and self.curvature_switch > 0 and self.huber_curvature < 1.0
         if huber:
             h.set_huber_curvature(1.0)
