@@ -164,6 +164,16 @@ PTZBA_EXPORT int ptzba_problem_info(ptzba_handle h, int64_t* info8);
  * [2] workgroups whose landmarks' frame range exceeds the LDS frame table, so they read the tables from global memory,
  * [3] the largest number of segment windows one landmark is walked in */
 PTZBA_EXPORT int ptzba_k1_info(ptzba_handle h, int64_t* info4);
+/* the linearisation kernel's record stream.  Pair-form input repeats an observation once per match it takes part in;
+ * ptzba_set_problem merges each run -- adjacent records of one (landmark, frame) segment, in its (landmark, frame,
+ * index) order, whose stored records (the delta pair in the record precision, the user weight) are bit-identical --
+ * into one record of weight multiplicity x user weight, and the kernel reads the merged stream when the runs are at
+ * most half the records.  out4: [0] runs (n_obs when the pass did not run: PTZBA_K1_MERGE=0, or the segments alone are
+ * more than half the records, so the runs cannot halve them), [1] 1 when the kernel reads the
+ * merged stream, [2] 1 when that stream holds exactly one record per segment and the kernel without a record phase
+ * runs (PTZBA_K1_ONE=0: the general kernel), [3] 0.  Both knobs are read by every ptzba_set_problem call (as
+ * PTZBA_K2_PIPE is), not once per handle.  ptzba_problem_info's n_obs stays the caller's record count. */
+PTZBA_EXPORT int ptzba_k1_merge_info(ptzba_handle h, int64_t* out4);
 /* the reduced-system kernel's work items (each runs its landmark list in batches of 16, two batches per round of
  * its operand ring): [0] items, [1] chunk-0 items (they also sum the diagonal terms), [2] / [3] shortest / longest
  * list, then how many items have [4] at most 16 landmarks (one batch), [5] nl % 32 in 1..16 (odd batch count),
@@ -721,6 +731,15 @@ PTZBA_EXPORT int ptz_orb(int device, int32_t width, int32_t height, const uint8_
  * landmark-sharded solve passes in ptzba_problem_opts. */
 PTZBA_EXPORT int ptzba_coupling_window(int32_t n_pose, int32_t n_landmark, int64_t n_obs, const int32_t* obs_frame,
                                        const int32_t* obs_landmark, int32_t* win_out);
+/* The runs ptzba_set_problem's host front merges for the linearisation kernel (ptzba_k1_merge_info), host only: the
+ * records sorted by (landmark, frame, index), precision PTZBA_FP64 / PTZBA_FP32 = the record precision the deltas are
+ * stored in, obs_weight may be NULL.  counts3: [0] segments, [1] runs, [2] 1 when the runs are at most half the
+ * records.  run_first [cap] (may be NULL): the original index of each run's first record; run_mult [cap] (may be
+ * NULL): its multiplicity; both in sorted order, at most cap written. */
+PTZBA_EXPORT int ptzba_k1_merge_runs(int32_t n_pose, int32_t n_landmark, int64_t n_obs, const int32_t* obs_frame,
+                                     const int32_t* obs_landmark, const double* obs_xy, const double* obs_weight,
+                                     int32_t precision, int64_t* counts3, int64_t cap, int64_t* run_first,
+                                     int64_t* run_mult);
 /* First-seen landmark ids over ordered pair match lists (image_process.py:611-639).
  * pair_i/pair_j/pair_count: n_pairs; idx_a/idx_b: concatenated match keypoint indices.
  * kp_count[n_frames]: keypoints per frame.  Output landmark id per match (of the src keypoint) and

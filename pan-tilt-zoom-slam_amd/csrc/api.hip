@@ -232,27 +232,37 @@ int ptzba::stage_take(ptzba_ctx* h, size_t n, uint8_t** out) {
 // ------------------------------------------------------------------------------------------------
 // records hold obs - base(segment) in `real`; the per-segment base observation stays fp64, so the
 // per-record arithmetic of K1 works on O(residual) magnitudes even in fp32
+// the host fronts' stored records, converted once (layout_convert_records): the merge pass compares them, the upload
+// copies them
+struct HostRecords {
+  std::vector<double> seg_base;
+  std::vector<uint8_t> xy, w;  // [2 n_rec] / [n_rec] (empty: unweighted) in the record precision
+};
 template <typename real>
-static int upload_records(ptzba_ctx* h, const std::vector<int64_t>& order, const std::vector<int32_t>& rec_seg,
-                          const std::vector<double>& base, const double* obs_xy, const double* w) {
-  // the copies below read host vectors that die at return: every exit path (errors included) waits for the
-  // handle's stream first (the stream does not order itself behind the legacy null stream, so every upload /
-  // memset of set_problem goes on h->st)
-  const size_t nxy = 2 * (size_t)h->n_rec, nw = w ? (size_t)h->n_rec : 0;
+static void convert_records(const ProblemLayout& L, int64_t n_obs, const double* obs_xy, const double* w, HostRecords& hr) {
+  hr.xy.resize(2 * (size_t)n_obs * sizeof(real));
+  hr.w.resize(w ? (size_t)n_obs * sizeof(real) : 0);
+  layout_convert_records<real>(L, n_obs, obs_xy, w, hr.seg_base, reinterpret_cast<real*>(hr.xy.data()),
+                               reinterpret_cast<real*>(hr.w.data()));
+}
+static int upload_records(ptzba_ctx* h, const HostRecords& hr) {
+  // the copies below read host vectors of set_problem: every exit path (errors included) waits for the handle's
+  // stream first (the stream does not order itself behind the legacy null stream, so every upload / memset of
+  // set_problem goes on h->st)
+  const size_t e = h->elem(), bxy = hr.xy.size(), bw = hr.w.size();
   // allocate everything before queuing any copy; padded by 8 records: K1's coarsened loads read whole groups
-  if (h->rec_xy.alloc((nxy + 16) * sizeof(real))) return -1;
-  if (w) {
-    if (h->rec_w.alloc(nw * sizeof(real))) return -1;
+  if (h->rec_xy.alloc(bxy + 16 * e)) return -1;
+  if (bw) {
+    if (h->rec_w.alloc(bw)) return -1;
   } else {
     h->rec_w.release();
   }
-  // small problems (a sliding window's ~170K records) convert straight into the pinned staging buffer and queue the
-  // copies; large ones convert into host vectors and copy with a synchronisation (the vectors die at return)
+  // small problems (a sliding window's ~170K records) go through the pinned staging buffer with set_problem's other
+  // staged uploads; large ones copy from the vectors with a synchronisation
   uint8_t *pxy = nullptr, *pw = nullptr;
-  if (stage_take(h, nxy * sizeof(real), &pxy)) return -1;
-  if (pxy && w && stage_take(h, nw * sizeof(real), &pw)) return -1;
-  const bool staged = pxy && (!w || pw);
-  std::vector<real> vxy(staged ? 0 : nxy), vw(staged ? 0 : nw);
+  if (stage_take(h, bxy, &pxy)) return -1;
+  if (pxy && bw && stage_take(h, bw, &pw)) return -1;
+  const bool staged = pxy && (!bw || pw);
   struct SyncIf {  // the vector path: every exit waits for the copies reading the vectors (errors included)
     hipStream_t s;
     bool on;
@@ -260,27 +270,21 @@ static int upload_records(ptzba_ctx* h, const std::vector<int64_t>& order, const
       if (on) (void)hipStreamSynchronize(s);
     }
   } sync_guard{h->st, !staged};
-  real* xy = staged ? reinterpret_cast<real*>(pxy) : vxy.data();
-  real* ww = staged ? reinterpret_cast<real*>(pw) : vw.data();
-  parallel_chunks(h->n_rec, host_threads(h->n_rec), [&](int64_t lo, int64_t hi, int) {
-    for (int64_t r = lo; r < hi; ++r) {
-      const int32_t s = rec_seg[r];
-      xy[2 * r] = (real)(obs_xy[2 * order[r]] - base[2 * s]);
-      xy[2 * r + 1] = (real)(obs_xy[2 * order[r] + 1] - base[2 * s + 1]);
-      if (w) ww[r] = (real)w[order[r]];
+  uint8_t* pad = h->rec_xy.as<uint8_t>() + bxy;
+  if (staged) {
+    std::memcpy(pxy, hr.xy.data(), bxy);
+    if (bw) std::memcpy(pw, hr.w.data(), bw);
+    if (h->stage_batch) {  // queued with set_problem's other staged uploads
+      h->stage_ops.push_back({h->rec_xy.p, (size_t)(pxy - h->stage), bxy});
+      if (bw) h->stage_ops.push_back({h->rec_w.p, (size_t)(pw - h->stage), bw});
+      return zero_async(h, pad, 16 * e);
     }
-  });
-  if (staged && h->stage_batch) {  // queued with set_problem's other staged uploads
-    h->stage_ops.push_back({h->rec_xy.p, (size_t)(pxy - h->stage), nxy * sizeof(real)});
-    if (w) h->stage_ops.push_back({h->rec_w.p, (size_t)(pw - h->stage), nw * sizeof(real)});
-    return zero_async(h, reinterpret_cast<real*>(h->rec_xy.p) + nxy, 16 * sizeof(real));
   }
-  HIPCHK(hipMemcpyAsync(h->rec_xy.p, xy, nxy * sizeof(real), hipMemcpyHostToDevice, h->st));
-  HIPCHK(hipMemsetAsync(reinterpret_cast<real*>(h->rec_xy.p) + nxy, 0, 16 * sizeof(real), h->st));
-  if (w) HIPCHK(hipMemcpyAsync(h->rec_w.p, ww, nw * sizeof(real), hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipMemcpyAsync(h->rec_xy.p, staged ? pxy : hr.xy.data(), bxy, hipMemcpyHostToDevice, h->st));
+  HIPCHK(hipMemsetAsync(pad, 0, 16 * e, h->st));
+  if (bw) HIPCHK(hipMemcpyAsync(h->rec_w.p, staged ? pw : hr.w.data(), bw, hipMemcpyHostToDevice, h->st));
   return 0;
 }
-
 
 // set_problem's device front for large problems (setup_kernels.hip): the records' (landmark, frame, index) order,
 // segments and device record arrays (rec_seg, seg_frame / seg_lm / seg_rec_begin, seg_base, rec_xy / rec_w, rec_key,
@@ -290,7 +294,7 @@ static int upload_records(ptzba_ctx* h, const std::vector<int64_t>& order, const
 // 2.2 ms on the host (set_problem per keyframe, config 5: keyframe BA 8.7-9.2 -> 7.9-8.1 ms mean, profiles/r06f_*)
 constexpr int64_t GPU_SETUP_MIN_REC = (int64_t)1 << 16;
 static int gpu_front(ptzba_ctx* h, int64_t n, int n_pose, int n_lm, const int32_t* frame, const int32_t* lm,
-                     const double* xy, const double* w, ProblemLayout& L) {
+                     const double* xy, const double* w, bool merge, ProblemLayout& L) {
   auto &seg_frame = L.seg_frame, &seg_lm = L.seg_lm;
   auto& seg_rec_begin = L.seg_rec_begin;
   DBuf order, key;
@@ -348,8 +352,70 @@ static int gpu_front(ptzba_ctx* h, int64_t n, int n_pose, int n_lm, const int32_
   if (rc) return rc;
   HIPCHK(hipMemsetAsync(h->rec_xy.as<uint8_t>() + 2 * (size_t)n * e, 0, 16 * e, h->st));  // K1's padded record groups
   HIPCHK(hipMemsetAsync(h->rec_key.as<uint8_t>() + n, 0, 8, h->st));
+  // K1's merged stream: the runs flagged and scanned over the stored records (the sort's order and keys are dead: the
+  // scan's scratch); built when the runs are at most half the records, with the padding K1 relies on above
+  DBuf m_first;
+  L.n_merged = n;
+  L.k1_merged = false;
+  if (merge && 2 * ns <= n) {  // (a run never spans segments: more segments than half the records cannot halve them)
+    int64_t nm = 0;
+    const int32_t* rs = h->rec_seg.as<int32_t>();
+    if (h->precision == PTZBA_FP32
+            ? setup_merge_runs<float>(h->st, n, rs, h->rec_xy.as<float>(), w ? h->rec_w.as<float>() : nullptr,
+                                      key.as<int32_t>(), order.as<int32_t>(), &nm)
+            : setup_merge_runs<double>(h->st, n, rs, h->rec_xy.as<double>(), w ? h->rec_w.as<double>() : nullptr,
+                                       key.as<int32_t>(), order.as<int32_t>(), &nm))
+      return -1;
+    L.n_merged = nm;
+    L.k1_merged = k1_merge_pays(nm, n);
+  }
+  if (L.k1_merged) {
+    const int64_t nm = L.n_merged;
+    if (m_first.alloc(4 * (size_t)(nm + 1)) || h->m_rec_xy.alloc((2 * (size_t)nm + 16) * e) || h->m_rec_w.alloc((size_t)nm * e) ||
+        h->m_rec_key.alloc((size_t)nm + 8) || h->m_seg_rec_begin.alloc(8 * (size_t)(ns + 1)))
+      return -1;
+    const int32_t* rs = h->rec_seg.as<int32_t>();
+    if (h->precision == PTZBA_FP32
+            ? setup_merge_fill<float>(h->st, n, ns, nm, rs, order.as<int32_t>(), h->rec_xy.as<float>(),
+                                      w ? h->rec_w.as<float>() : nullptr, h->rec_key.as<uint8_t>(), m_first.as<uint32_t>(),
+                                      h->m_rec_xy.as<float>(), h->m_rec_w.as<float>(), h->m_rec_key.as<uint8_t>(),
+                                      h->m_seg_rec_begin.as<int64_t>())
+            : setup_merge_fill<double>(h->st, n, ns, nm, rs, order.as<int32_t>(), h->rec_xy.as<double>(),
+                                       w ? h->rec_w.as<double>() : nullptr, h->rec_key.as<uint8_t>(), m_first.as<uint32_t>(),
+                                       h->m_rec_xy.as<double>(), h->m_rec_w.as<double>(), h->m_rec_key.as<uint8_t>(),
+                                       h->m_seg_rec_begin.as<int64_t>()))
+      return -1;
+    HIPCHK(hipMemsetAsync(h->m_rec_xy.as<uint8_t>() + 2 * (size_t)nm * e, 0, 16 * e, h->st));
+    HIPCHK(hipMemsetAsync(h->m_rec_key.as<uint8_t>() + nm, 0, 8, h->st));
+    L.m_seg_rec_begin.resize(ns + 1);
+    HIPCHK(hipMemcpyAsync(L.m_seg_rec_begin.data(), h->m_seg_rec_begin.p, 8 * (size_t)(ns + 1), hipMemcpyDeviceToHost, h->st));
+  }
   HIPCHK(hipStreamSynchronize(h->st));  // the temporaries and the host vectors' copies above complete here
   return 0;
+}
+
+// the host fronts' merged stream (ProblemLayout::m_first): each run's stored record, its key, multiplicity x user weight
+template <typename real>
+static int upload_merged(ptzba_ctx* h, const ProblemLayout& L, const HostRecords& hr) {
+  const int64_t nm = L.n_merged;
+  const real* sxy = reinterpret_cast<const real*>(hr.xy.data());
+  const real* sw = hr.w.empty() ? nullptr : reinterpret_cast<const real*>(hr.w.data());
+  std::vector<real> xy(2 * (size_t)nm + 16, (real)0), ww((size_t)nm);  // + 8 records, + 8 keys: K1 reads whole groups
+  std::vector<uint8_t> key((size_t)nm + 8, 0);
+  parallel_chunks(nm, host_threads(nm), [&](int64_t lo, int64_t hi, int) {
+    for (int64_t m = lo; m < hi; ++m) {
+      const int64_t k = L.m_first[m];
+      const int32_t sg = L.rec_seg[k];
+      xy[2 * m] = sxy[2 * k];
+      xy[2 * m + 1] = sxy[2 * k + 1];
+      ww[m] = (real)(L.m_first[m + 1] - k) * (sw ? sw[k] : (real)1);
+      key[m] = (uint8_t)((sg - L.lm_seg_begin[L.seg_lm[sg]]) % K1_SEGW);
+    }
+  });
+  return upload_st(h, h->m_rec_xy, xy) || upload_st(h, h->m_rec_w, ww) || upload_st(h, h->m_rec_key, key) ||
+                 upload_st(h, h->m_seg_rec_begin, L.m_seg_rec_begin)
+             ? -1
+             : 0;
 }
 
 // host phase times of a set_problem call (ptzba_setup_timing: where a config-4 set_problem spends its seconds)
@@ -368,10 +434,9 @@ struct PhaseClock {
 // call order below.
 static int upload_problem(ptzba_ctx* h, const ProblemLayout& L, const SysOrder& sorder, const CholPlan& plan,
                           const TreePlan& tplan, bool gpu_setup, bool part_mode, const std::vector<uint8_t>& row_phase,
-                          const std::vector<uint8_t>& fmask, const double* obs_xy, const double* obs_weight,
-                          PhaseClock& st_mark) {
+                          const std::vector<uint8_t>& fmask, const HostRecords& hr, PhaseClock& st_mark) {
   const int n_pose = h->n_pose, n_landmark = h->n_lm;
-  const int64_t n_obs = h->n_rec, n_seg = h->n_seg;
+  const int64_t n_obs = h->n_rec;
   // ---- upload (staged: the stream has drained, so the staging buffer is free)
   HIPCHK(hipStreamSynchronize(h->st));
   h->stage_used = 0;
@@ -384,16 +449,8 @@ static int upload_problem(ptzba_ctx* h, const ProblemLayout& L, const SysOrder& 
   } batch_off{h};
   st_mark("pre-upload sync");
   if (!gpu_setup) {  // (the device front has built these on the device)
-    std::vector<double> seg_base(2 * n_seg);
-    for (int64_t s = 0; s < n_seg; ++s) {
-      const int64_t r = L.order[L.seg_rec_begin[s]];
-      seg_base[2 * s] = obs_xy[2 * r];
-      seg_base[2 * s + 1] = obs_xy[2 * r + 1];
-    }
-    int rc = h->precision == PTZBA_FP32 ? upload_records<float>(h, L.order, L.rec_seg, seg_base, obs_xy, obs_weight)
-                                        : upload_records<double>(h, L.order, L.rec_seg, seg_base, obs_xy, obs_weight);
-    if (rc) return rc;
-    if (upload_st(h, h->seg_base, seg_base)) return -1;
+    if (upload_records(h, hr)) return -1;
+    if (upload_st(h, h->seg_base, hr.seg_base)) return -1;
     {  // K1's 1-byte segment key: the record's segment within its landmark's window of K1_SEGW segments
       std::vector<uint8_t> key(n_obs + 8);  // + 8: K1 reads whole 8-record key groups
       for (int64_t k = 0; k < n_obs; ++k) {
@@ -405,6 +462,14 @@ static int upload_problem(ptzba_ctx* h, const ProblemLayout& L, const SysOrder& 
     if (upload_st(h, h->rec_seg, L.rec_seg) || upload_st(h, h->seg_frame, L.seg_frame) || upload_st(h, h->seg_lm, L.seg_lm) ||
         upload_st(h, h->seg_rec_begin, L.seg_rec_begin))
       return -1;
+    if (L.k1_merged && (h->precision == PTZBA_FP32 ? upload_merged<float>(h, L, hr)
+                                                   : upload_merged<double>(h, L, hr)))
+      return -1;
+  }
+  if (L.k1_merged) {
+    if (upload_st(h, h->lm_order_m, L.lm_work_m)) return -1;
+  } else {  // a problem whose runs do not halve its records keeps today's memory
+    for (DBuf* b : {&h->m_rec_xy, &h->m_rec_w, &h->m_rec_key, &h->m_seg_rec_begin, &h->lm_order_m}) b->release();
   }
   h->s2_groups_host = L.s2_groups;
   if (upload_st(h, h->lm_seg_begin, L.lm_seg_begin) ||
@@ -591,16 +656,31 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
                          (uint64_t)n_landmark * (uint64_t)n_pose <= ((uint64_t)1 << 32);
   // the host fronts sort by two stable counting passes (the device front sorts in its segment phase)
   ProblemLayout L;
+  HostRecords hr;
+  // PTZBA_K1_MERGE=0: K1 keeps the unmerged record stream (A/B and the parity tests)
+  const bool k1_merge = !getenv_is("PTZBA_K1_MERGE", "0");
   const int threads = host_threads(n_obs);
   const bool par_host = !gpu_setup && threads > 1;
   if (!gpu_setup) layout_host_sort(L, n_pose, n_landmark, n_obs, obs_frame, obs_landmark, threads);
   st_mark("sort");
   if (gpu_setup) {
-    if (gpu_front(h, n_obs, n_pose, n_landmark, obs_frame, obs_landmark, obs_xy, obs_weight, L)) return -1;
+    if (gpu_front(h, n_obs, n_pose, n_landmark, obs_frame, obs_landmark, obs_xy, obs_weight, k1_merge, L)) return -1;
     lm_first_segments(L, n_landmark);
   } else if (const char* e = layout_host_segments(L, n_landmark, n_obs, obs_frame, obs_landmark, threads)) {
     return fail("%s", e);
+  } else {
+    // the stored records, converted once: the merge pass compares them, upload_problem copies them
+    if (o.precision == PTZBA_FP32) convert_records<float>(L, n_obs, obs_xy, obs_weight, hr);
+    else convert_records<double>(L, n_obs, obs_xy, obs_weight, hr);
+    L.n_merged = n_obs;
+    // (a run never spans segments: with more segments than half the records the pass cannot halve them and is skipped)
+    if (k1_merge && 2 * (int64_t)L.seg_frame.size() <= n_obs)
+      layout_host_merge(L, n_obs, hr.xy.data(), hr.w.empty() ? nullptr : hr.w.data(), o.precision == PTZBA_FP32, threads);
   }
+  h->n_merged = L.n_merged;
+  h->k1_merged = L.k1_merged;
+  // pair-form input whose repeats are all adjacent: one merged record per segment (PTZBA_K1_ONE=0: the general kernel)
+  h->k1_one = L.k1_merged && L.n_merged == (int64_t)L.seg_frame.size() && !getenv_is("PTZBA_K1_ONE", "0");
   h->n_seg = (int64_t)L.seg_frame.size();
   layout_frame_csr(L, n_pose, par_host || gpu_setup, threads);
   st_mark("segments+frame csr");
@@ -717,7 +797,7 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   if (gpu_setup) h->perm_host.clear();
 
   st_mark("work order+plan");
-  if (upload_problem(h, L, sorder, plan, tplan, gpu_setup, part_mode, row_phase, fmask, obs_xy, obs_weight, st_mark)) return -1;
+  if (upload_problem(h, L, sorder, plan, tplan, gpu_setup, part_mode, row_phase, fmask, hr, st_mark)) return -1;
   if (!gpu_setup) h->perm_host = std::move(L.order);
   st_mark("final sync");
   h->have_problem = true;
@@ -786,6 +866,16 @@ int ptzba_k1_info(ptzba_handle h, int64_t* info) {
   return 0;
 }
 
+int ptzba_k1_merge_info(ptzba_handle h, int64_t* out4) {
+  if (!h || !h->have_problem) return fail("no problem set");
+  if (!out4) return fail("bad arguments");
+  out4[0] = h->n_merged;
+  out4[1] = h->k1_merged ? 1 : 0;
+  out4[2] = h->k1_one ? 1 : 0;
+  out4[3] = 0;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 static void* ft_real(ptzba_ctx* h) { return h->precision == PTZBA_FP32 ? h->ft.p : h->ft64.p; }
 static void* rt_real(ptzba_ctx* h) { return h->precision == PTZBA_FP32 ? h->rt.p : h->rt64.p; }
@@ -808,15 +898,18 @@ void ptzba::tables(ptzba_ctx* h, const double* ptz, const double* rays, const in
 void ptzba::linearize_into(ptzba_ctx* h, int slot, const int* sel, int sel_xor, const int* run_if, const double* hc_dev,
                            bool trial_state) {
   LinArgs a;
-  a.lm_work = h->lm_order.as<int4>();
+  // the merged record stream when the problem has one; ptzba_marginal_prior's per-record weights split runs, so a
+  // launch under w_override reads the unmerged records
+  const bool merged = h->k1_merged && !h->w_override;
+  a.lm_work = (merged ? h->lm_order_m : h->lm_order).as<int4>();
   a.n_work = h->n_work;
   a.lm_seg_begin = h->lm_seg_begin.as<int32_t>();
   a.seg_frame = h->seg_frame.as<int32_t>();
-  a.seg_rec_begin = h->seg_rec_begin.as<int64_t>();
+  a.seg_rec_begin = (merged ? h->m_seg_rec_begin : h->seg_rec_begin).as<int64_t>();
   a.rec_seg = h->rec_seg.as<int32_t>();
-  a.rec_key = h->rec_key.as<uint8_t>();
-  a.rec_xy = h->rec_xy.p;
-  a.rec_w = h->w_override ? h->w_override : (h->weighted ? h->rec_w.p : nullptr);
+  a.rec_key = (merged ? h->m_rec_key : h->rec_key).as<uint8_t>();
+  a.rec_xy = merged ? h->m_rec_xy.p : h->rec_xy.p;
+  a.rec_w = merged ? h->m_rec_w.p : (h->w_override ? h->w_override : (h->weighted ? h->rec_w.p : nullptr));
   a.ft = ft_real(h);
   a.rt = rt_real(h);
   a.ft64 = h->ft64.p;
@@ -846,7 +939,10 @@ void ptzba::linearize_into(ptzba_ctx* h, int slot, const int* sel, int sel_xor, 
   a.n_pose = h->n_pose;
   if (!run_if) tm_begin(h, TM_K1);
   hipEvent_t e0 = run_if ? nullptr : tm_k1_event(h, 0), e1 = run_if ? nullptr : tm_k1_event(h, 1);
-  if (h->precision == PTZBA_FP32)
+  if (merged && h->k1_one) {  // one merged record per segment: the kernel without a record phase (k1_one_kernel.hip)
+    if (h->precision == PTZBA_FP32) launch_linearize_one<float>(a, h->loss, h->st, e0, e1);
+    else launch_linearize_one<double>(a, h->loss, h->st, e0, e1);
+  } else if (h->precision == PTZBA_FP32)
     launch_linearize<float>(a, h->loss, h->st, e0, e1);
   else
     launch_linearize<double>(a, h->loss, h->st, e0, e1);

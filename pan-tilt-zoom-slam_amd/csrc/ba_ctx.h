@@ -42,6 +42,13 @@ struct ptzba_ctx {
   // device: structure
   DBuf rec_xy, rec_seg, rec_w, perm, rec_key;
   DBuf seg_frame, seg_lm, seg_rec_begin, lm_seg_begin, lm_order;
+  // K1's merged record stream (problem_layout.h): runs of adjacent bit-identical records of a segment as one record of
+  // weight multiplicity x user weight; allocated only while k1_merged.  Every other reader of the records (residual,
+  // covariance, marginal prior, K1 under w_override) keeps the unmerged arrays above
+  DBuf m_rec_xy, m_rec_w, m_rec_key, m_seg_rec_begin, lm_order_m;
+  int64_t n_merged = 0;    // runs (n_rec when the pass did not run: the knob, or more segments than half the records)
+  bool k1_merged = false;  // K1 reads the merged stream: the runs are at most half the records
+  bool k1_one = false;     // ... and it holds exactly one record per segment (k_linearize_one; PTZBA_K1_ONE=0: off)
   DBuf seg_row;  // [n_seg] system row of the segment's frame, -1: fixed (k_trial; launch_seg_row in set_problem)
   DBuf frame_seg_begin, frame_seg_list, frame_win_hi;
   DBuf s2_items, s2_groups, s2_lm, lm_meta;  // K2 work items / tiles / lists, slot ranges

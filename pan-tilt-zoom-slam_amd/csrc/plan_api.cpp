@@ -7,6 +7,8 @@
 #include "../../include/ptzba.h"
 #include "chol_plan.h"
 #include "host_util.h"
+#include "par_util.h"
+#include "problem_layout.h"
 
 using namespace ptzba;
 
@@ -22,6 +24,44 @@ int ptzba_coupling_window(int32_t n_pose, int32_t n_landmark, int64_t n_obs, con
   }
   for (int f = 0; f < n_pose; ++f) win_out[f] = f;
   for (int64_t r = 0; r < n_obs; ++r) win_out[obs_frame[r]] = std::max(win_out[obs_frame[r]], hi[obs_landmark[r]]);
+  return 0;
+}
+
+// host only: the runs set_problem's host front merges for K1 (problem_layout.h), from the same passes
+int ptzba_k1_merge_runs(int32_t n_pose, int32_t n_landmark, int64_t n_obs, const int32_t* obs_frame,
+                        const int32_t* obs_landmark, const double* obs_xy, const double* obs_weight, int32_t precision,
+                        int64_t* counts3, int64_t cap, int64_t* run_first, int64_t* run_mult) {
+  if (n_pose < 1 || n_landmark < 0 || n_obs < 0 || !counts3 || (n_obs > 0 && (!obs_frame || !obs_landmark || !obs_xy)) ||
+      (precision != PTZBA_FP64 && precision != PTZBA_FP32))
+    return fail("bad arguments");
+  for (int64_t r = 0; r < n_obs; ++r)
+    if (obs_frame[r] < 0 || obs_frame[r] >= n_pose || obs_landmark[r] < 0 || obs_landmark[r] >= n_landmark)
+      return fail("record %lld out of range", (long long)r);
+  ProblemLayout L;
+  const int threads = host_threads(n_obs);
+  layout_host_sort(L, n_pose, n_landmark, n_obs, obs_frame, obs_landmark, threads);
+  if (const char* e = layout_host_segments(L, n_landmark, n_obs, obs_frame, obs_landmark, threads)) return fail("%s", e);
+  std::vector<double> seg_base, xy64, w64;
+  std::vector<float> xy32, w32;
+  const bool fp32 = precision == PTZBA_FP32;
+  if (fp32) {
+    xy32.resize(2 * (size_t)n_obs);
+    w32.resize(obs_weight ? (size_t)n_obs : 0);
+    layout_convert_records<float>(L, n_obs, obs_xy, obs_weight, seg_base, xy32.data(), w32.data());
+    layout_host_merge(L, n_obs, xy32.data(), obs_weight ? w32.data() : nullptr, true, threads, true);
+  } else {
+    xy64.resize(2 * (size_t)n_obs);
+    w64.resize(obs_weight ? (size_t)n_obs : 0);
+    layout_convert_records<double>(L, n_obs, obs_xy, obs_weight, seg_base, xy64.data(), w64.data());
+    layout_host_merge(L, n_obs, xy64.data(), obs_weight ? w64.data() : nullptr, false, threads, true);
+  }
+  counts3[0] = (int64_t)L.seg_frame.size();
+  counts3[1] = L.n_merged;
+  counts3[2] = L.k1_merged ? 1 : 0;
+  for (int64_t m = 0; m < std::min(cap, L.n_merged); ++m) {
+    if (run_first) run_first[m] = L.order[L.m_first[m]];
+    if (run_mult) run_mult[m] = L.m_first[m + 1] - L.m_first[m];
+  }
   return 0;
 }
 

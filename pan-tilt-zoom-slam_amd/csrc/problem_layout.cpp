@@ -2,6 +2,7 @@
 #include "problem_layout.h"
 
 #include <algorithm>
+#include <cstring>
 #include <utility>
 
 #include "ptzba_kernels.h"
@@ -105,6 +106,75 @@ const char* layout_host_segments(ProblemLayout& L, int n_lm, int64_t n_obs, cons
   }
   L.seg_rec_begin.push_back(n_obs);  // (the device front returns the end entry with the segments)
   return nullptr;
+}
+
+// ---- the stored records of the host fronts: deltas from each segment's base observation in the record precision
+template <typename real>
+void layout_convert_records(const ProblemLayout& L, int64_t n_obs, const double* obs_xy, const double* w,
+                            std::vector<double>& seg_base, real* xy, real* ww) {
+  const int64_t n_seg = (int64_t)L.seg_frame.size();
+  seg_base.resize(2 * n_seg);
+  for (int64_t s = 0; s < n_seg; ++s) {
+    const int64_t r = L.order[L.seg_rec_begin[s]];
+    seg_base[2 * s] = obs_xy[2 * r];
+    seg_base[2 * s + 1] = obs_xy[2 * r + 1];
+  }
+  const auto &order = L.order;
+  const auto& rec_seg = L.rec_seg;
+  parallel_chunks(n_obs, host_threads(n_obs), [&](int64_t lo, int64_t hi, int) {
+    for (int64_t r = lo; r < hi; ++r) {
+      const int32_t s = rec_seg[r];
+      xy[2 * r] = (real)(obs_xy[2 * order[r]] - seg_base[2 * s]);
+      xy[2 * r + 1] = (real)(obs_xy[2 * order[r] + 1] - seg_base[2 * s + 1]);
+      if (w) ww[r] = (real)w[order[r]];
+    }
+  });
+}
+template void layout_convert_records<float>(const ProblemLayout&, int64_t, const double*, const double*,
+                                            std::vector<double>&, float*, float*);
+template void layout_convert_records<double>(const ProblemLayout&, int64_t, const double*, const double*,
+                                             std::vector<double>&, double*, double*);
+
+// ---- K1's merged stream: runs of adjacent bit-identical stored records inside a segment
+template <typename real>
+static void host_merge(ProblemLayout& L, int64_t n_obs, const real* xy, const real* w, int threads, bool fill_always) {
+  const auto& rec_seg = L.rec_seg;
+  const int64_t n_seg = (int64_t)L.seg_frame.size();
+  // on the stored arrays, as the device front does (bits compared: -0.0 and +0.0 differ); cheap enough to evaluate in
+  // the counting pass and again in the fill
+  auto is_start = [&](int64_t k) {
+    return k == 0 || rec_seg[k] != rec_seg[k - 1] || std::memcmp(xy + 2 * k, xy + 2 * k - 2, 2 * sizeof(real)) != 0 ||
+           (w && std::memcmp(w + k, w + k - 1, sizeof(real)) != 0);
+  };
+  const int T = std::max(threads, 1);
+  std::vector<int64_t> base(T + 1, 0);
+  parallel_chunks(n_obs, T, [&](int64_t lo, int64_t hi, int t) {
+    int64_t c = 0;
+    for (int64_t k = lo; k < hi; ++k) c += is_start(k);
+    base[t + 1] = c;
+  });
+  for (int t = 0; t < T; ++t) base[t + 1] += base[t];
+  L.n_merged = base[T];
+  L.k1_merged = k1_merge_pays(L.n_merged, n_obs);
+  if (!L.k1_merged && !fill_always) return;
+  L.m_first.resize(L.n_merged + 1);
+  L.m_seg_rec_begin.resize(n_seg + 1);
+  parallel_chunks(n_obs, T, [&](int64_t lo, int64_t hi, int t) {
+    int64_t m = base[t];
+    for (int64_t k = lo; k < hi; ++k)
+      if (is_start(k)) {
+        if (k == 0 || rec_seg[k] != rec_seg[k - 1]) L.m_seg_rec_begin[rec_seg[k]] = m;
+        L.m_first[m++] = k;
+      }
+  });
+  L.m_first[L.n_merged] = n_obs;
+  L.m_seg_rec_begin[n_seg] = L.n_merged;
+}
+
+void layout_host_merge(ProblemLayout& L, int64_t n_obs, const void* rec_xy, const void* rec_w, bool fp32, int threads,
+                       bool fill_always) {
+  if (fp32) host_merge<float>(L, n_obs, (const float*)rec_xy, (const float*)rec_w, threads, fill_always);
+  else host_merge<double>(L, n_obs, (const double*)rec_xy, (const double*)rec_w, threads, fill_always);
 }
 
 void lm_first_segments(ProblemLayout& L, int n_lm) {
@@ -308,6 +378,8 @@ const char* layout_k2(ProblemLayout& L, int n_pose, int n_lm, int n_fixed) {
 void layout_k1_order(ProblemLayout& L, int n_pose, int n_lm) {
   const auto &lm_seg_begin = L.lm_seg_begin, &lm_meta = L.lm_meta;
   const auto& seg_rec_begin = L.seg_rec_begin;
+  // the record stream K1 reads: the order weighs a landmark by its work there
+  const auto& k1_rec_begin = L.k1_merged ? L.m_seg_rec_begin : L.seg_rec_begin;
   auto& lm_work = L.lm_work;
   std::vector<int32_t> lm_order;
   L.max_seg = 0;
@@ -320,7 +392,7 @@ void layout_k1_order(ProblemLayout& L, int n_pose, int n_lm) {
     // heaviest first (LPT over the workgroup slots) at 1/8-octave resolution of the record count, and inside such a
     // size class by first frame: a K1 workgroup's landmarks then see neighbouring frames, so it stages ~a coupling
     // window of frame tables instead of the whole table (ba_kernels.hip FTL)
-    auto nrec = [&](int l) { return seg_rec_begin[lm_seg_begin[l + 1]] - seg_rec_begin[lm_seg_begin[l]]; };
+    auto nrec = [&](int l) { return k1_rec_begin[lm_seg_begin[l + 1]] - k1_rec_begin[lm_seg_begin[l]]; };
     auto size_class = [&](int l) {
       const uint64_t c = (uint64_t)nrec(l);
       if (c < 16) return (int)c;
@@ -343,6 +415,15 @@ void layout_k1_order(ProblemLayout& L, int n_pose, int n_lm) {
     lm_work[8 * k + 3] = (int32_t)seg_rec_begin[lm_seg_begin[l]];
     for (int q = 0; q < 3; ++q) lm_work[8 * k + 4 + q] = lm_meta[4 * l + q];
     lm_work[8 * k + 7] = (int32_t)seg_rec_begin[std::min(lm_seg_begin[l + 1], lm_seg_begin[l] + K1_SEGW)];
+  }
+  L.lm_work_m.clear();
+  if (L.k1_merged) {  // the same descriptors with the merged stream's record bounds
+    L.lm_work_m = lm_work;
+    for (int k = 0; k < L.n_work; ++k) {
+      const int l = lm_order[k];
+      L.lm_work_m[8 * k + 3] = (int32_t)L.m_seg_rec_begin[lm_seg_begin[l]];
+      L.lm_work_m[8 * k + 7] = (int32_t)L.m_seg_rec_begin[std::min(lm_seg_begin[l + 1], lm_seg_begin[l] + K1_SEGW)];
+    }
   }
   // which table path each K1 workgroup takes (ptzba_k1_info): the kernel's own frame range and predicate
   L.k1_groups = (L.n_work + K1_WPB - 1) / K1_WPB;

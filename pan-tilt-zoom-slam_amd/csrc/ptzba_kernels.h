@@ -263,6 +263,9 @@ template <typename real>
 // ev0 / ev1 != nullptr: the launch carries the event pair itself (hipExtLaunchKernelGGL: the kernel packet's own
 // start / end timestamps, no marker packets around it)
 void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// k1_one_kernel.hip: K1 on a (merged) record stream with exactly one record per segment, weights given
+template <typename real>
+void launch_linearize_one(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 template <typename real>
 void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, int pipe);
 // scratch: RED_SCRATCH doubles (partials + counter), zero-initialised once, reused across calls
@@ -569,5 +572,16 @@ template <typename real>
 int setup_records(hipStream_t st, int64_t n, int64_t n_seg, const uint32_t* order, const int32_t* rec_seg,
                   const int32_t* seg_lm, const int64_t* seg_rec_begin, const int32_t* lm_first, const double* xy,
                   const double* w, double* seg_base, real* rec_xy, real* rec_w, uint8_t* rec_key, int64_t* perm);
+// K1's merged stream (problem_layout.h): run_id [n] = the inclusive scan of the run starts over the stored records
+// (flag [n]: scratch), *n_merged = the number of runs (synchronises the stream)
+template <typename real>
+int setup_merge_runs(hipStream_t st, int64_t n, const int32_t* rec_seg, const real* rec_xy, const real* rec_w,
+                     int32_t* flag, int32_t* run_id, int64_t* n_merged);
+// the runs as K1 records: m_xy [2 n_merged], m_w [n_merged] = multiplicity x user weight, m_key [n_merged], the segments'
+// CSR into them m_seg_rec_begin [n_seg + 1]; m_first [n_merged + 1]: scratch (each run's first record)
+template <typename real>
+int setup_merge_fill(hipStream_t st, int64_t n, int64_t n_seg, int64_t n_merged, const int32_t* rec_seg,
+                     const int32_t* run_id, const real* rec_xy, const real* rec_w, const uint8_t* rec_key,
+                     uint32_t* m_first, real* m_xy, real* m_w, uint8_t* m_key, int64_t* m_seg_rec_begin);
 
 }  // namespace ptzba

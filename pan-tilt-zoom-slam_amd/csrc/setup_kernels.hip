@@ -12,6 +12,9 @@
 //   setup_records        the per-segment base observation (fp64, the segment's first record), the records as deltas
 //                        from it in the record precision, weights, K1's 1-byte window keys, the sorted -> original
 //                        permutation
+//   setup_merge_runs     K1's merged stream: the starts of the runs of adjacent bit-identical stored records inside a
+//   setup_merge_fill     segment flagged and inclusive-scanned; each run as one record of weight multiplicity x user
+//                        weight, its key, the segments' CSR into the runs (built when the runs halve the records)
 // The host keeps what its structure passes read (segment frame / landmark / first record); nothing here depends on
 // the host's thread count, so the result is the same bit for bit as the host path's.
 #include <rocprim/device/device_radix_sort.hpp>
@@ -82,6 +85,52 @@ __global__ void k_setup_records(int64_t n, const uint32_t* __restrict__ order, c
   }
 }
 
+// ---- K1's merged stream: a run is a maximal sequence of adjacent records of one segment whose stored records (delta
+// pair, weight) are bit-identical (-0.0 and +0.0 differ) -- the host pass's rule (problem_layout.cpp host_merge)
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+template <typename real>
+__global__ void k_merge_flags(int64_t n, const int32_t* __restrict__ rec_seg, const real* __restrict__ rec_xy,
+                              const real* __restrict__ rec_w, int32_t* __restrict__ flag) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    bool start = k == 0 || rec_seg[k] != rec_seg[k - 1];
+    if (!start)
+      start = !same_bits(rec_xy[2 * k], rec_xy[2 * k - 2]) || !same_bits(rec_xy[2 * k + 1], rec_xy[2 * k - 1]) ||
+              (rec_w && !same_bits(rec_w[k], rec_w[k - 1]));
+    flag[k] = start ? 1 : 0;
+  }
+}
+
+// run_id: the inclusive scan of the flags (1-based)
+template <typename real>
+__global__ void k_merge_fill(int64_t n, int64_t n_seg, int64_t n_merged, const int32_t* __restrict__ rec_seg,
+                             const int32_t* __restrict__ run_id, const real* __restrict__ rec_xy,
+                             const uint8_t* __restrict__ rec_key, uint32_t* __restrict__ m_first, real* __restrict__ m_xy,
+                             uint8_t* __restrict__ m_key, int64_t* __restrict__ m_seg_rec_begin) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = run_id[k] - 1;
+    if (k == 0 || run_id[k - 1] != run_id[k]) {
+      m_first[m] = (uint32_t)k;
+      m_xy[2 * m] = rec_xy[2 * k];
+      m_xy[2 * m + 1] = rec_xy[2 * k + 1];
+      m_key[m] = rec_key[k];
+      if (k == 0 || rec_seg[k] != rec_seg[k - 1]) m_seg_rec_begin[rec_seg[k]] = m;
+    }
+    if (k == n - 1) {
+      m_first[n_merged] = (uint32_t)n;
+      m_seg_rec_begin[n_seg] = n_merged;
+    }
+  }
+}
+
+template <typename real>
+__global__ void k_merge_weights(int64_t n_merged, const uint32_t* __restrict__ m_first, const real* __restrict__ rec_w,
+                                real* __restrict__ m_w) {
+  for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < n_merged; m += (int64_t)gridDim.x * blockDim.x)
+    m_w[m] = (real)(int64_t)(m_first[m + 1] - m_first[m]) * (rec_w ? rec_w[m_first[m]] : (real)1);
+}
+
 dim3 grid_for(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)); }
 
 }  // namespace
@@ -143,6 +192,48 @@ int setup_records(hipStream_t st, int64_t n, int64_t n_seg, const uint32_t* orde
   HIPCHK(hipGetLastError());
   return 0;
 }
+
+template <typename real>
+int setup_merge_runs(hipStream_t st, int64_t n, const int32_t* rec_seg, const real* rec_xy, const real* rec_w,
+                     int32_t* flag, int32_t* run_id, int64_t* n_merged) {
+  *n_merged = 0;
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL((k_merge_flags<real>), grid_for(n), dim3(256), 0, st, n, rec_seg, rec_xy, rec_w, flag);
+  HIPCHK(hipGetLastError());
+  DBuf temp;
+  size_t sb = 0;
+  HIPCHK(rocprim::inclusive_scan(nullptr, sb, flag, run_id, (size_t)n, rocprim::plus<int32_t>(), st));
+  if (temp.alloc(sb)) return -1;
+  HIPCHK(rocprim::inclusive_scan(temp.p, sb, flag, run_id, (size_t)n, rocprim::plus<int32_t>(), st));
+  int32_t last = 0;
+  HIPCHK(hipMemcpyAsync(&last, run_id + (n - 1), 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // (also: the scan's temporary dies at return)
+  *n_merged = last;
+  return 0;
+}
+
+template <typename real>
+int setup_merge_fill(hipStream_t st, int64_t n, int64_t n_seg, int64_t n_merged, const int32_t* rec_seg,
+                     const int32_t* run_id, const real* rec_xy, const real* rec_w, const uint8_t* rec_key,
+                     uint32_t* m_first, real* m_xy, real* m_w, uint8_t* m_key, int64_t* m_seg_rec_begin) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL((k_merge_fill<real>), grid_for(n), dim3(256), 0, st, n, n_seg, n_merged, rec_seg, run_id, rec_xy,
+                     rec_key, m_first, m_xy, m_key, m_seg_rec_begin);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL((k_merge_weights<real>), grid_for(n_merged), dim3(256), 0, st, n_merged, m_first, rec_w, m_w);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+template int setup_merge_runs<float>(hipStream_t, int64_t, const int32_t*, const float*, const float*, int32_t*, int32_t*,
+                                     int64_t*);
+template int setup_merge_runs<double>(hipStream_t, int64_t, const int32_t*, const double*, const double*, int32_t*,
+                                      int32_t*, int64_t*);
+template int setup_merge_fill<float>(hipStream_t, int64_t, int64_t, int64_t, const int32_t*, const int32_t*, const float*,
+                                     const float*, const uint8_t*, uint32_t*, float*, float*, uint8_t*, int64_t*);
+template int setup_merge_fill<double>(hipStream_t, int64_t, int64_t, int64_t, const int32_t*, const int32_t*,
+                                      const double*, const double*, const uint8_t*, uint32_t*, double*, double*, uint8_t*,
+                                      int64_t*);
 
 template int setup_records<float>(hipStream_t, int64_t, int64_t, const uint32_t*, const int32_t*, const int32_t*,
                                   const int64_t*, const int32_t*, const double*, const double*, double*, float*, float*,

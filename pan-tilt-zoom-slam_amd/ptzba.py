@@ -173,6 +173,7 @@ def lib():
         "ptzba_set_problem": ([V, I32, I32, I64, V, V, V, V, D, D, POINTER(ptzba_problem_opts)], I),
         "ptzba_problem_info": ([V, V], I),
         "ptzba_k1_info": ([V, V], I),
+        "ptzba_k1_merge_info": ([V, V], I),
         "ptzba_k2_info": ([V, V], I),
         "ptzba_k2_tile_info": ([V, V], I),
         "ptzba_build_info": ([V, V], I),
@@ -227,6 +228,7 @@ def lib():
         "ptz_h_jacobian": ([I, I64, D, D, D, D, D, V, V, V], I),
         "ptzba_build_landmarks": ([I32, V, I64, V, V, V, V, V, V, V, V], I),
         "ptzba_coupling_window": ([I32, I32, I64, V, V, V], I),
+        "ptzba_k1_merge_runs": ([I32, I32, I64, V, V, V, V, I32, V, I64, V, V], I),
         "ptzba_plan_summary": ([I32, I32, V, I32, V], I),
         "ptzba_plan_export": ([I32, I32, V, I32, V, V, I64, V, I64, V], I),
         "ptz_match_knn2": ([I, I64, I64, I32, V, V, V, V], I),
@@ -289,11 +291,11 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "ptzba_new", "ptzba_delete", "ptzba_last_error", "ptzba_version", "ptzba_set_stream", "ptzba_use_own_stream", "ptzba_set_problem",
-    "ptzba_problem_info", "ptzba_k1_info", "ptzba_k2_info", "ptzba_k2_tile_info", "ptzba_build_info", "ptzba_schur_groups", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
+    "ptzba_problem_info", "ptzba_k1_info", "ptzba_k1_merge_info", "ptzba_k2_info", "ptzba_k2_tile_info", "ptzba_build_info", "ptzba_schur_groups", "ptzba_solver_info", "ptzba_residual", "ptzba_set_state", "ptzba_get_state", "ptzba_linearize",
     "ptzba_build_reduced", "ptzba_solve_reduced", "ptzba_step", "ptzba_set_huber_curvature", "ptzba_set_setup_front", "ptzba_setup_timing", "ptzba_solve", "ptzba_solve_resident", "ptzba_read_scalars", "ptzba_accept",
     "ptzba_lm_start", "ptzba_lm_init", "ptzba_lm_build", "ptzba_lm_solve", "ptzba_lm_decide", "ptzba_lm_wait",
     "ptzba_exchange", "ptzba_exchange_packed", "ptzba_pack", "ptzba_unpack", "ptzba_sync", "ptzba_kernel_times", "ptzba_reset_kernel_times", "ptzba_comm_times", "ptzba_dist_form_estimate", "ptzba_save_state", "ptzba_restore_state", "ptz_ray_to_image",
-    "ptz_image_to_ray", "ptz_project_rays", "ptz_back_project_rays", "ptz_h_jacobian", "ptzba_build_landmarks", "ptzba_coupling_window", "ptz_match_knn2", "ptz_homography_ransac", "ptz_homography_ransac_batch", "ptz_lk_track", "ptz_sift", "ptz_match_hamming",
+    "ptz_image_to_ray", "ptz_project_rays", "ptz_back_project_rays", "ptz_h_jacobian", "ptzba_build_landmarks", "ptzba_coupling_window", "ptzba_k1_merge_runs", "ptz_match_knn2", "ptz_homography_ransac", "ptz_homography_ransac_batch", "ptz_lk_track", "ptz_sift", "ptz_match_hamming",
     "ptz_py_shuffle_prefix", "ptz_set_order_pairs", "ptz_keyframe_features", "ptz_pack_records",
     "ptz_refine_poses", "ptzekf_new", "ptzekf_delete", "ptzekf_num_rays", "ptzekf_set_state", "ptzekf_get_state", "ptzekf_add_pose_cov",
     "ptzekf_remove_rays", "ptzekf_add_rays", "ptzekf_project_visible", "ptzekf_update",
@@ -803,6 +805,27 @@ def frame_coupling_window(n_pose, frame, landmark):
     _check(lib().ptzba_coupling_window(int(n_pose), n_lm, len(frame), _ptr(frame), _ptr(landmark), _ptr(win)),
            "ptzba_coupling_window")
     return win
+
+
+def k1_merge_runs(n_pose, n_landmark, frame, landmark, xy, weight=None, precision=FP64):
+    """The runs set_problem's host front merges for the linearisation kernel (ptzba_k1_merge_runs, host only): adjacent
+    records of one (landmark, frame) segment, in (landmark, frame, index) order, whose stored records -- the delta pair
+    in the record precision and the user weight -- are bit-identical.  Returns (segments, runs, halves, first, mult):
+    the counts, whether the runs are at most half the records, and per run the original index of its first record and
+    its multiplicity."""
+    frame = np.ascontiguousarray(frame, np.int32)
+    landmark = np.ascontiguousarray(landmark, np.int32)
+    xy = np.ascontiguousarray(xy, np.float64)
+    w = None if weight is None else np.ascontiguousarray(weight, np.float64)
+    n = len(frame)
+    counts = np.zeros(3, np.int64)
+    first = np.zeros(max(n, 1), np.int64)
+    mult = np.zeros(max(n, 1), np.int64)
+    _check(lib().ptzba_k1_merge_runs(int(n_pose), int(n_landmark), n, _ptr(frame), _ptr(landmark), _ptr(xy),
+                                     None if w is None else _ptr(w), int(precision), _ptr(counts), n, _ptr(first),
+                                     _ptr(mult)), "ptzba_k1_merge_runs")
+    m = int(counts[1])
+    return int(counts[0]), m, bool(counts[2]), first[:m].copy(), mult[:m].copy()
 
 
 def check_pose_priors(factors, n_pose=None):
@@ -1440,6 +1463,16 @@ class BAHandle:
         out = np.zeros(4, np.int64)
         _check(lib().ptzba_k1_info(self.h, _ptr(out)), "ptzba_k1_info")
         return [int(x) for x in out]
+
+    def k1_merge_info(self):
+        """The linearisation kernel's record stream (ptzba_k1_merge_info) as a dict: `runs` -- the runs of adjacent
+        bit-identical records of a segment (the record count when the pass did not run: PTZBA_K1_MERGE=0, or
+        more segments than half the records) --, `merged` --
+        the kernel reads the merged stream (the runs are at most half the records) --, `one_record` -- that stream has
+        exactly one record per segment and the kernel without a record phase runs (k_linearize_one)."""
+        out = np.zeros(4, np.int64)
+        _check(lib().ptzba_k1_merge_info(self.h, _ptr(out)), "ptzba_k1_merge_info")
+        return {"runs": int(out[0]), "merged": bool(out[1]), "one_record": bool(out[2])}
 
     def k2_info(self):
         """The reduced-system kernel's work items (ptzba_k2_info): items, chunk-0 items, shortest / longest landmark
