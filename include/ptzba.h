@@ -464,6 +464,26 @@ PTZBA_EXPORT int ptzba_set_ray_priors(ptzba_handle h, const ptzba_ray_priors* pr
 /* out4: [0] priors, [1] distinct landmarks under a prior, [2] prior rows (2 n_prior), [3] the ray-prior cost
  * 1/2 sum_k e_k^T Lambda_k e_k at the handle's current state (0 without ray priors) */
 PTZBA_EXPORT int ptzba_ray_prior_info(ptzba_handle h, double* out4);
+/* Projection-centre displacement (ptzba_version 0.9): the reference PTZCamera's K (R p + d(f)) in the
+ * bundle adjuster, the camera the tracker (ptz_project_rays, ptzekf_update, ptz_h_jacobian) already projects with.
+ * With r = R_x(tilt) R_y(pan) p and lambda = displacement6,
+ *     q = r + (l0 + l3 f, l1 + l4 f, l2 + l5 f),     x = u + f q0 / q2,     y = v + f q1 / |q2|
+ * (lambda = 0: the model of every earlier version).  lambda is a constant of the problem, not a variable: the pose
+ * Jacobian's f column gains d(x, y)/dq (l3, l4, l5), d(x, y)/dq is formed at the displaced q, and the structure of the
+ * solve is unchanged.  Every path that projects follows: ptzba_linearize / step / accept, ptzba_lm_*, ptzba_solve,
+ * ptzba_solve_resident, ptzba_residual, ptzba_covariance and ptzba_covariance_joint (the residual scale included) and
+ * ptzba_marginal_prior.  ptz_refine_poses, ptz_pose_ransac and the ray map stay displacement-free.
+ *
+ * The six values are copied.  NULL or six zeros clears the displacement: the handle then launches the kernels it
+ * launches without this call, bit for bit.  Valid after ptzba_set_problem, between solves; cleared by
+ * ptzba_set_problem; persistent over ptzba_set_state / ptzba_save_state / ptzba_restore_state; independent of the pose
+ * priors, the ray priors and the marginal factor (all may be set together).
+ * Refused with a message, the handle left as it was: a non-finite value; a pending LM trial; (for a non-zero
+ * displacement) a sharded handle, or one with a communicator or hook attached or a caller-run exchange protocol in
+ * use.  While a displacement is set, ptzba_attach_comm and ptzba_set_exchange_hook are refused. */
+PTZBA_EXPORT int ptzba_set_displacement(ptzba_handle h, const double* displacement6);
+/* out8: [0] 1 = a displacement is active, [1..6] lambda (zeros when none), [7] 0 */
+PTZBA_EXPORT int ptzba_displacement_info(ptzba_handle h, double* out8);
 /* Which front builds the record arrays in the following ptzba_set_problem calls of this handle (round 6): the device
  * front (one rocPRIM radix sort + segment / record kernels) from min_records records on, the host's counting sorts
  * below.  0: always the device, INT64_MAX: never, -1: the default (64K records since round 6, 4M before: configs 3 and 4

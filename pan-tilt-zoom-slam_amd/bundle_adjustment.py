@@ -125,7 +125,7 @@ class _KeyframeLists:
 def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, center, rotation, u, v, save_path,
                       verbose=False, precision="fp64", loss="linear", f_scale=1.0, ftol=1e-4, xtol=1e-8,
                       max_iter=100, device=0, correspondences=None, *, covariance=False, pose_priors=None,
-                      marginal_prior=None, marginalize=None, ray_priors=None):
+                      marginal_prior=None, marginalize=None, ray_priors=None, displacement=None):
     """bundle_adjustment.py:109-251 on the MI355X path.  Returns (landmarks [M,2], keyframes).
     covariance=True (keyword only; off: the call and its outputs are unchanged): a third element, a dict with
     `pose_cov` [N,3,3] (pan, tilt, f; row i belongs to keyframes[i], the fixed frame 0 all zero), `ray_cov` [M,2,2]
@@ -152,6 +152,10 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     that no match of the call uses is skipped and its key listed in LAST_RESULT["ray_priors_skipped"];
     LAST_RESULT["ray_priors_used"] is the number of priors set.  ptzba.ray_priors_from_result builds the list from a
     covariance=True result.
+    displacement (keyword only; None or all zero: the call and its outputs are unchanged): the camera's six
+    projection-centre displacement values (PTZCamera.displacement).  The adjustment then runs under the camera the
+    tracker projects with, K (R p + d(f)) (ptzba.BAHandle.set_displacement), and each ray starts from
+    ptzba.back_project_rays with the same displacement -- the same source record and last-writer rule as without.
     `correspondences`: optional correspondence.CorrespondenceCache keyed by image_indices, so repeated
     calls over growing / sliding keyframe sets only detect new images and match new pairs."""
     import correspondence
@@ -164,6 +168,12 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
     assert initial_ptzs.shape[0] == N and initial_ptzs.shape[1] == 3
     assert np.asarray(center).shape[0] == 3 and np.asarray(rotation).shape == (3, 3)
     assert feature_method in ("sift", "orb", "latch")
+    if displacement is not None:
+        displacement = np.asarray(displacement, np.float64).reshape(-1)
+        if displacement.shape != (6,) or not np.isfinite(displacement).all():
+            raise ValueError("displacement: six finite values expected")
+        if not np.any(displacement != 0):
+            displacement = None
     priors = None
     if pose_priors:
         where = {k: i for i, k in enumerate(image_indices)}
@@ -240,10 +250,17 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         lids = np.flatnonzero(has)
         rec = src_rec[has]
         fi = frame[rec]
-        th, ph = ptzba.image_to_ray(u, v, initial_ptzs[fi, 2], initial_ptzs[fi, 0], initial_ptzs[fi, 1], xy[rec, 0],
-                                    xy[rec, 1], device=device)
-        rays0[lids, 0] = th
-        rays0[lids, 1] = ph
+        if displacement is None:
+            th, ph = ptzba.image_to_ray(u, v, initial_ptzs[fi, 2], initial_ptzs[fi, 0], initial_ptzs[fi, 1], xy[rec, 0],
+                                        xy[rec, 1], device=device)
+            rays0[lids, 0] = th
+            rays0[lids, 1] = ph
+        else:
+            # the displaced camera's back-projection, one batch per source frame
+            for f in np.unique(fi).tolist():
+                at = fi == f
+                rays0[lids[at]] = ptzba.back_project_rays(u, v, initial_ptzs[f, 2], initial_ptzs[f, 0],
+                                                          initial_ptzs[f, 1], xy[rec[at]], displacement, device=device)
     rpriors, rp_skipped = None, []
     if ray_keys is not None:
         # (frame, keypoint) -> landmark through the call's matches, the first match in loop order winning
@@ -276,7 +293,7 @@ def bundle_adjustment(images, image_indices, feature_method, initial_ptzs, cente
         out = ptzba.solve(N, n_landmark, frame, lm, xy, u, v, initial_ptzs, rays0, precision=prec, loss=ls,
                           f_scale=f_scale, device=device, ftol=ftol, xtol=xtol, max_iter=max_iter,
                           covariance=cov_arg if covariance else None, pose_priors=priors, marginal_prior=marg,
-                          marginalize=leaving, ray_priors=rpriors or None)
+                          marginalize=leaving, ray_priors=rpriors or None, displacement=displacement)
         all_poses, landmarks, res = out[:3]
         if leaving is not None:
             marg_out = dict(marginal=out[-1]["marginal"].reindex(dict(enumerate(image_indices))), stats=out[-1]["stats"])

@@ -99,11 +99,11 @@ const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.7: ptzba_build_info (read-only counters of the builds' launch path).
 // 0.8: ptzba_covariance_joint (ptzba_cov_opts as 0.3).
 // 0.9: PTZBA_LOSS_SOFT_L1 / _CAUCHY / _ARCTAN (no struct changes; huber_curvature / curvature_switch are read for
-// every robust loss).
+// every robust loss); ptzba_set_displacement / ptzba_displacement_info (no struct changes).
 const char* ptzba_version(void) {
   return "ptzba 0.9 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
          "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors as 0.6; ptzba_build_info as 0.7; ptzba_covariance_joint "
-         "as ptzba 0.8; losses soft_l1 / cauchy / arctan)";
+         "as ptzba 0.8; losses soft_l1 / cauchy / arctan; ptzba_set_displacement)";
 }
 
 ptzba_handle ptzba_new(int device) {
@@ -630,6 +630,8 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   h->mg.release_work();
   h->cov.release_joint();  // ... and without ptzba_covariance_joint's workspace
   h->rp.n_prior = 0;    // ... and without ray priors
+  h->displaced = false;  // ... and without a projection-centre displacement
+  for (double& d : h->disp) d = 0.0;
   h->w_override = nullptr;
   h->trial_open = false;
   h->ptz_saved.release();
@@ -937,6 +939,11 @@ void ptzba::linearize_into(ptzba_ctx* h, int slot, const int* sel, int sel_xor, 
   a.w_slot1 = h->w_slot[1].p;
   a.lm_out1 = h->lm_out[1].as<double>();
   a.n_pose = h->n_pose;
+  a.displaced = h->displaced;
+  for (int k = 0; k < 6; ++k) {
+    a.disp[k] = h->disp[k];
+    a.disp32[k] = (float)h->disp[k];
+  }
   if (!run_if) tm_begin(h, TM_K1);
   hipEvent_t e0 = run_if ? nullptr : tm_k1_event(h, 0), e1 = run_if ? nullptr : tm_k1_event(h, 1);
   if (merged && h->k1_one) {  // one merged record per segment: the kernel without a record phase (k1_one_kernel.hip)
@@ -996,11 +1003,11 @@ int ptzba_residual(ptzba_handle h, const double* x_full, double* r_out) {
   if (h->precision == PTZBA_FP32)
     launch_residual<float>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
                            h->seg_base.as<double2>(), h->rec_xy.p, h->perm.as<int64_t>(), h->ft64.p, h->rt64.p, h->u,
-                           h->v, h->n_rec, r.as<double>(), h->st);
+                           h->v, h->disp6(), h->n_rec, r.as<double>(), h->st);
   else
     launch_residual<double>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
                             h->seg_base.as<double2>(), h->rec_xy.p, h->perm.as<int64_t>(), h->ft64.p, h->rt64.p, h->u,
-                            h->v, h->n_rec, r.as<double>(), h->st);
+                            h->v, h->disp6(), h->n_rec, r.as<double>(), h->st);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(r_out, r.p, 2 * (size_t)h->n_rec * 8, hipMemcpyDeviceToHost, h->st));
   HIPCHK(hipStreamSynchronize(h->st));
@@ -1680,6 +1687,7 @@ int ptzba_set_exchange_hook(ptzba_handle h, ptzba_exchange_fn fn, void* ctx) {
   if (fn && h->has_marg()) return fail("ptzba_set_exchange_hook: the handle has a marginal prior set (single rank only)");
   if (fn && h->has_priors()) return fail("ptzba_set_exchange_hook: the handle has pose priors set (single rank only)");
   if (fn && h->has_ray_priors()) return fail("ptzba_set_exchange_hook: the handle has ray priors set (single rank only)");
+  if (fn && h->displaced) return fail("ptzba_set_exchange_hook: the handle has a displacement set (single rank only)");
   h->hook = fn;
   h->hook_ctx = ctx;
   return 0;
@@ -1690,6 +1698,7 @@ int ptzba_attach_comm(ptzba_handle h, ptzba_comm comm) {
   if (comm && h->has_marg()) return fail("ptzba_attach_comm: the handle has a marginal prior set (single rank only)");
   if (comm && h->has_priors()) return fail("ptzba_attach_comm: the handle has pose priors set (single rank only)");
   if (comm && h->has_ray_priors()) return fail("ptzba_attach_comm: the handle has ray priors set (single rank only)");
+  if (comm && h->displaced) return fail("ptzba_attach_comm: the handle has a displacement set (single rank only)");
   h->drop_groups();
   h->comm = comm;
   return 0;  // the group communicator is split lazily by the first exchange (collective, every rank reaches it)

@@ -143,12 +143,12 @@ static int cov_front(ptzba_ctx* h, const ptzba_cov_opts& opt) {
     if (h->precision == PTZBA_FP32)
       launch_cov_resid<float>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
                               h->seg_base.as<double2>(), h->rec_xy.p, h->weighted ? h->rec_w.p : nullptr, h->ft64.p,
-                              h->rt64.p, h->u, h->v, h->n_rec, h->loss, h->fs, resid + 8, n_part,
+                              h->rt64.p, h->u, h->v, h->disp6(), h->n_rec, h->loss, h->fs, resid + 8, n_part,
                               resid, h->st);
     else
       launch_cov_resid<double>(h->rec_seg.as<int32_t>(), h->seg_frame.as<int32_t>(), h->seg_lm.as<int32_t>(),
                                h->seg_base.as<double2>(), h->rec_xy.p, h->weighted ? h->rec_w.p : nullptr, h->ft64.p,
-                               h->rt64.p, h->u, h->v, h->n_rec, h->loss, h->fs, resid + 8, n_part,
+                               h->rt64.p, h->u, h->v, h->disp6(), h->n_rec, h->loss, h->fs, resid + 8, n_part,
                                resid, h->st);
   }
   // ... + sum_k e_k^T Lambda_k e_k, twice the prior cost

@@ -208,6 +208,12 @@ struct ptzba_ctx {
     DBuf lm, begin, mean, info;
     DBuf cost;  // [1] ptzba_ray_prior_info's read-back
   } rp;
+  // projection-centre displacement (ptzba_set_displacement): d(f) = disp[0..2] + disp[3..5] f, a constant of
+  // the problem.  It changes what K1, the residual and the covariance's residual scale project and nothing else, so
+  // the slot tables, K2 and the fused prepare stay as they are
+  bool displaced = false;
+  double disp[6] = {0, 0, 0, 0, 0, 0};
+  const double* disp6() const { return displaced ? disp : nullptr; }  // the launchers' argument (nullptr: none)
   std::vector<int32_t> win_host, pos_host;  // the problem's coupling window and system positions (prior validation)
   // marginalisation (ptzba_marginal_prior / ptzba_set_marginal_prior; marg_kernels.hip)
   struct Marg {

@@ -179,8 +179,12 @@ __device__ long long g_k1_items[32768][8];  // start, end, A, B, C, final, segme
 // FTL: the frame tables are staged in LDS (n_pose <= K1_FT_LDS): phase A's chain is descriptor -> segment frame id
 // -> LDS instead of descriptor -> frame id -> global frame table (one dependent memory latency less per wave)
 // WT: records carry multiplicities (rec_w; the dedup form) -- unweighted problems keep no weight registers
-template <typename real, int LOSS, bool FTL, bool WT = true>
+// DISP: the displaced camera model (ptzba_common.h ptz_project_disp; LinArgs::disp) in phase A's projection and phase
+// C's Jacobian; the other instantiations compile the source they always did.  LDS-table form only: it serves any
+// n_pose (a workgroup whose frame range exceeds the table reads global memory), the global-table form is an A/B build
+template <typename real, int LOSS, bool FTL, bool WT = true, bool DISP = false>
 __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_MIN_WAVES64) void k_linearize(LinArgs a) {
+  static_assert(FTL || !DISP, "the displaced model is instantiated for the LDS-table form only");
   __shared__ real s_x[K1_WPB][SEGW], s_y[K1_WPB][SEGW], s_acc[K1_WPB][4][SEGW];
   __shared__ double s_ft[5][FTL ? K1_FT_LDS : 1];  // ca, sa, cb, sb, f per frame (fp64)
   const int lane = lane_id();
@@ -415,7 +419,10 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
         const int fs = a.seg_frame[s];
         fsv[i] = fs;
         double x, y;
-        if constexpr (FTL) ptz_project<double>(ft_lds(fs), R64, a.u, a.v, x, y);
+        if constexpr (DISP) {
+          const double dc[3] = {a.disp[0], a.disp[1], a.disp[2]}, dk[3] = {a.disp[3], a.disp[4], a.disp[5]};
+          ptz_project_disp<double>(ft_lds(fs), R64, a.u, a.v, dc, dk, x, y);  // (LDS, or global when !ftl_ok)
+        } else if constexpr (FTL) ptz_project<double>(ft_lds(fs), R64, a.u, a.v, x, y);
         else ptz_project<double>(ft64[fs], R64, a.u, a.v, x, y);
         const double2 bs = seg_base[s];
         sx[sl] = (real)(x - bs.x);
@@ -453,7 +460,21 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
       const int sl = s - w0;
       real x, y, J[2][5];
       const int fs = fsv[i];
-      if (FTL && !ftl_ok) {
+      if constexpr (DISP) {
+        // the record-precision frame table from the global fallback or from LDS, then the displaced Jacobian
+        real dc[3], dk[3];
+        lin_disp<real>(a, dc, dk);
+        FrameTab<real> F;
+        if (!ftl_ok) {
+          F = ft[fs];
+        } else {
+          const int fl = fs - fbase;
+          F.ca = (real)s_ft[0][fl]; F.sa = (real)s_ft[1][fl]; F.cb = (real)s_ft[2][fl]; F.sb = (real)s_ft[3][fl];
+          F.f = (real)s_ft[4][fl];
+          F.pad0 = F.pad1 = F.pad2 = (real)0;
+        }
+        ptz_project_jac_disp<real>(F, R, u, v, dc, dk, x, y, J);
+      } else if (FTL && !ftl_ok) {
         ptz_project_jac<real>(ft[fs], R, u, v, x, y, J);
       } else if constexpr (FTL) {
         // the record-precision table is the rounded fp64 one (k_tables): the same values as ft[fs]
@@ -525,9 +546,12 @@ void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0
   };
   const bool wt = a.rec_w != nullptr;
   // one instantiation per loss (the template value is the PTZBA_LOSS_* id), frame-table path and weight form
+  // (the displaced model: the LDS-table form only, which serves any n_pose -- one extra instantiation per loss and
+  // weight form, not two)
   auto pick = [&](auto loss_c) {
     constexpr int L = decltype(loss_c)::value;
-    if (ftl) wt ? go(k_linearize<real, L, true, true>) : go(k_linearize<real, L, true, false>);
+    if (a.displaced) wt ? go(k_linearize<real, L, true, true, true>) : go(k_linearize<real, L, true, false, true>);
+    else if (ftl) wt ? go(k_linearize<real, L, true, true>) : go(k_linearize<real, L, true, false>);
     else wt ? go(k_linearize<real, L, false, true>) : go(k_linearize<real, L, false, false>);
   };
   switch (loss) {
@@ -999,17 +1023,19 @@ void launch_reduce_cols(const double* src, int64_t n, int stride, int nk, int ma
 // ------------------------------------------------------------------------------------------------
 // record-order residual (parity API for bundle_adjustment._compute_residual)
 // ------------------------------------------------------------------------------------------------
-template <typename real>
+// DISP: the displaced camera model (ptzba_common.h), d = its six constants
+template <typename real, bool DISP>
 __global__ void k_residual(const int32_t* __restrict__ rec_seg, const int32_t* __restrict__ seg_frame,
                            const int32_t* __restrict__ seg_lm, const double2* __restrict__ seg_base,
                            const real* __restrict__ rec_xy, const int64_t* __restrict__ perm,
                            const FrameTab<double>* __restrict__ ft64, const RayTab<double>* __restrict__ rt64,
-                           double u, double v, int64_t n_rec, double* __restrict__ r_out) {
+                           double u, double v, Disp6 d, int64_t n_rec, double* __restrict__ r_out) {
   int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rec) return;
   const int s = rec_seg[r];
   double x, y;
-  ptz_project<double>(ft64[seg_frame[s]], rt64[seg_lm[s]], u, v, x, y);
+  if constexpr (DISP) ptz_project_disp<double>(ft64[seg_frame[s]], rt64[seg_lm[s]], u, v, d.c, d.k, x, y);
+  else ptz_project<double>(ft64[seg_frame[s]], rt64[seg_lm[s]], u, v, x, y);
   const double2 bs = seg_base[s];
   const real ex = (real)(x - bs.x), ey = (real)(y - bs.y);
   const int64_t o = perm[r];
@@ -1020,11 +1046,15 @@ __global__ void k_residual(const int32_t* __restrict__ rec_seg, const int32_t* _
 template <typename real>
 void launch_residual(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                      const void* rec_xy, const int64_t* perm, const void* ft64, const void* rt64, double u, double v,
-                     int64_t n_rec, double* r_out, hipStream_t st) {
+                     const double* disp6, int64_t n_rec, double* r_out, hipStream_t st) {
   if (n_rec <= 0) return;
-  hipLaunchKernelGGL(k_residual<real>, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, rec_seg, seg_frame,
-                     seg_lm, seg_base, (const real*)rec_xy, perm, (const FrameTab<double>*)ft64,
-                     (const RayTab<double>*)rt64, u, v, n_rec, r_out);
+  auto go = [&](auto kern, const Disp6& d) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, rec_seg, seg_frame, seg_lm,
+                       seg_base, (const real*)rec_xy, perm, (const FrameTab<double>*)ft64,
+                       (const RayTab<double>*)rt64, u, v, d, n_rec, r_out);
+  };
+  if (disp6) go(k_residual<real, true>, make_disp6(disp6));
+  else go(k_residual<real, false>, Disp6{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1165,11 +1195,11 @@ template void launch_trial<float>(const BacksubArgs&, const double*, const doubl
 template void launch_trial<double>(const BacksubArgs&, const double*, const double*, const double*, double*, double*,
                                    int, void*, void*, void*, void*, hipStream_t, const uint8_t*, const int*);
 template void launch_residual<float>(const int32_t*, const int32_t*, const int32_t*, const double2*, const void*,
-                                     const int64_t*, const void*, const void*, double, double, int64_t, double*,
-                                     hipStream_t);
+                                     const int64_t*, const void*, const void*, double, double, const double*, int64_t,
+                                     double*, hipStream_t);
 template void launch_residual<double>(const int32_t*, const int32_t*, const int32_t*, const double2*, const void*,
-                                      const int64_t*, const void*, const void*, double, double, int64_t, double*,
-                                      hipStream_t);
+                                      const int64_t*, const void*, const void*, double, double, const double*, int64_t,
+                                      double*, hipStream_t);
 
 }  // namespace ptzba
 

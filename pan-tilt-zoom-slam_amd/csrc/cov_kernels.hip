@@ -348,8 +348,8 @@ template void launch_cov_joint<double>(const CovArgs&, const CovCrossArgs&, hipS
 
 // sum over the scalar residuals of w rho'(z) r^2 (z = (r / f_scale)^2; rho' = 1 for the linear loss and inside the
 // huber unit, 1 / sqrt(z) beyond, robust_loss.h's for the smooth losses; `loss` a PTZBA_LOSS_* id): per-workgroup
-// partials in a fixed order, summed by the last launch's one workgroup
-template <typename real>
+// partials in a fixed order, summed by the last launch's one workgroup.  DISP: the displaced camera model, d its constants
+template <typename real, bool DISP>
 __global__ __launch_bounds__(256) void k_cov_resid_part(const int32_t* __restrict__ rec_seg,
                                                         const int32_t* __restrict__ seg_frame,
                                                         const int32_t* __restrict__ seg_lm,
@@ -357,14 +357,15 @@ __global__ __launch_bounds__(256) void k_cov_resid_part(const int32_t* __restric
                                                         const real* __restrict__ rec_xy, const real* __restrict__ rec_w,
                                                         const FrameTab<double>* __restrict__ ft64,
                                                         const RayTab<double>* __restrict__ rt64, double u, double v,
-                                                        int64_t n_rec, int loss, double inv_fs2,
+                                                        Disp6 d, int64_t n_rec, int loss, double inv_fs2,
                                                         double* __restrict__ part) {
   __shared__ double red[256 / WAVE];
   double s = 0.0;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rec; r += (int64_t)gridDim.x * blockDim.x) {
     const int sg = rec_seg[r];
     double x, y;
-    ptz_project<double>(ft64[seg_frame[sg]], rt64[seg_lm[sg]], u, v, x, y);
+    if constexpr (DISP) ptz_project_disp<double>(ft64[seg_frame[sg]], rt64[seg_lm[sg]], u, v, d.c, d.k, x, y);
+    else ptz_project<double>(ft64[seg_frame[sg]], rt64[seg_lm[sg]], u, v, x, y);
     const double2 bs = seg_base[sg];
     const double ex = (double)((real)(x - bs.x) - rec_xy[2 * r]), ey = (double)((real)(y - bs.y) - rec_xy[2 * r + 1]);
     double qx = ex * ex, qy = ey * ey;
@@ -400,17 +401,22 @@ __global__ void k_cov_resid_sum(const double* __restrict__ part, int n, double* 
 template <typename real>
 void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                       const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
-                      int64_t n_rec, int loss, double f_scale, double* part, int n_part, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(k_cov_resid_part<real>, dim3(n_part), dim3(256), 0, st, rec_seg, seg_frame, seg_lm, seg_base,
-                     (const real*)rec_xy, (const real*)rec_w, (const FrameTab<double>*)ft64,
-                     (const RayTab<double>*)rt64, u, v, n_rec, loss, 1.0 / (f_scale * f_scale), part);
+                      const double* disp6, int64_t n_rec, int loss, double f_scale, double* part, int n_part,
+                      double* out, hipStream_t st) {
+  auto go = [&](auto kern, const Disp6& d) {
+    hipLaunchKernelGGL(kern, dim3(n_part), dim3(256), 0, st, rec_seg, seg_frame, seg_lm, seg_base,
+                       (const real*)rec_xy, (const real*)rec_w, (const FrameTab<double>*)ft64,
+                       (const RayTab<double>*)rt64, u, v, d, n_rec, loss, 1.0 / (f_scale * f_scale), part);
+  };
+  if (disp6) go(k_cov_resid_part<real, true>, make_disp6(disp6));
+  else go(k_cov_resid_part<real, false>, Disp6{});
   hipLaunchKernelGGL(k_cov_resid_sum, dim3(1), dim3(64), 0, st, part, n_part, out);
 }
 template void launch_cov_resid<float>(const int32_t*, const int32_t*, const int32_t*, const double2*, const void*,
-                                      const void*, const void*, const void*, double, double, int64_t, int, double,
-                                      double*, int, double*, hipStream_t);
+                                      const void*, const void*, const void*, double, double, const double*, int64_t,
+                                      int, double, double*, int, double*, hipStream_t);
 template void launch_cov_resid<double>(const int32_t*, const int32_t*, const int32_t*, const double2*, const void*,
-                                       const void*, const void*, const void*, double, double, int64_t, int, double,
-                                       double*, int, double*, hipStream_t);
+                                       const void*, const void*, const void*, double, double, const double*, int64_t,
+                                       int, double, double*, int, double*, hipStream_t);
 
 }  // namespace ptzba

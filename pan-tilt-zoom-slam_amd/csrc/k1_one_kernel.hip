@@ -46,7 +46,8 @@ __device__ __forceinline__ void total6(double (&v)[6]) {
   total_step6<0x143, 0xc>(v);
 }
 
-template <typename real, int LOSS>
+// DISP: the displaced camera model (ptzba_common.h; LinArgs::disp) in the fp64 projection and in the Jacobian
+template <typename real, int LOSS, bool DISP = false>
 __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
   __shared__ double s_ft[5][K1_FT_LDS];  // ca, sa, cb, sb, f per staged frame (fp64)
   const int lane = lane_id();
@@ -114,7 +115,12 @@ __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
       F64 = ((const FrameTab<double>*)a.ft64)[fs];
     }
     double x64, y64;
-    ptz_project<double>(F64, R64, a.u, a.v, x64, y64);
+    if constexpr (DISP) {
+      const double dc[3] = {a.disp[0], a.disp[1], a.disp[2]}, dk[3] = {a.disp[3], a.disp[4], a.disp[5]};
+      ptz_project_disp<double>(F64, R64, a.u, a.v, dc, dk, x64, y64);
+    } else {
+      ptz_project<double>(F64, R64, a.u, a.v, x64, y64);
+    }
     const double2 bs = a.seg_base[s];
     const real rx = (real)(x64 - bs.x) - ox, ry = (real)(y64 - bs.y) - oy;
     // the record's robust terms (k_linearize's consume_c): gradient weights wx, wy = w rho', Hessian weights hx, hy
@@ -153,7 +159,18 @@ __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
     const real Sx = hx, Sy = hy, Srx = wx * rx, Sry = wy * ry;
     // the segment's Jacobian and blocks (k_linearize's phase C)
     real x, y, J[2][5];
-    if (ftl_ok) {
+    if constexpr (DISP) {
+      real dc[3], dk[3];
+      lin_disp<real>(a, dc, dk);
+      FrameTab<real> F;
+      if (ftl_ok) {
+        F.ca = (real)F64.ca; F.sa = (real)F64.sa; F.cb = (real)F64.cb; F.sb = (real)F64.sb; F.f = (real)F64.f;
+        F.pad0 = F.pad1 = F.pad2 = (real)0;
+      } else {
+        F = ((const FrameTab<real>*)a.ft)[fs];
+      }
+      ptz_project_jac_disp<real>(F, R, u, v, dc, dk, x, y, J);
+    } else if (ftl_ok) {
       FrameTab<real> F;
       F.ca = (real)F64.ca; F.sa = (real)F64.sa; F.cb = (real)F64.cb; F.sb = (real)F64.sb; F.f = (real)F64.f;
       F.pad0 = F.pad1 = F.pad2 = (real)0;
@@ -198,6 +215,16 @@ void launch_linearize_one(const LinArgs& a, int loss, hipStream_t st, hipEvent_t
     if (ev0) hipExtLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, ev0, ev1, 0, a);
     else hipLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, a);
   };
+  if (a.displaced) {
+    switch (loss) {
+      case PTZBA_LOSS_LINEAR: go(k_linearize_one<real, PTZBA_LOSS_LINEAR, true>); break;
+      case PTZBA_LOSS_HUBER: go(k_linearize_one<real, PTZBA_LOSS_HUBER, true>); break;
+      case PTZBA_LOSS_SOFT_L1: go(k_linearize_one<real, PTZBA_LOSS_SOFT_L1, true>); break;
+      case PTZBA_LOSS_CAUCHY: go(k_linearize_one<real, PTZBA_LOSS_CAUCHY, true>); break;
+      default: go(k_linearize_one<real, PTZBA_LOSS_ARCTAN, true>); break;
+    }
+    return;
+  }
   switch (loss) {
     case PTZBA_LOSS_LINEAR: go(k_linearize_one<real, PTZBA_LOSS_LINEAR>); break;
     case PTZBA_LOSS_HUBER: go(k_linearize_one<real, PTZBA_LOSS_HUBER>); break;

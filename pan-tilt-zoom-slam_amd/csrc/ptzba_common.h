@@ -111,6 +111,68 @@ __device__ __forceinline__ void ptz_project_jac(const FrameTab<real>& F, const R
   J[1][4] = fy * e1 + fyz * e2;
 }
 
+// Displaced model (ptzba_set_displacement): the projection centre sits d(f) = c + k f away from the
+// rotation centre, the reference PTZCamera's  K (R p + d(f)):
+//   r = R_x(tilt) R_y(pan) p,   q = r + (c0 + k0 f, c1 + k1 f, c2 + k2 f),   x = u + f q0/q2,   y = v + f q1/|q2|
+// c = displacement6[0..2], k = displacement6[3..5], uniform per launch; d is formed from F.f in registers (three FMAs),
+// no table grows.  With c = k = 0 these are ptz_project / ptz_project_jac.
+template <typename real>
+__device__ __forceinline__ void ptz_project_disp(const FrameTab<real>& F, const RayTab<real>& R, real u, real v,
+                                                 const real (&dc)[3], const real (&dk)[3], real& x, real& y) {
+  real w0 = F.ca * R.p0 - F.sa;
+  real w2 = F.sa * R.p0 + F.ca;
+  real q0 = w0 + (dc[0] + dk[0] * F.f);
+  real q1 = F.cb * R.p1 + F.sb * w2 + (dc[1] + dk[1] * F.f);
+  real q2 = -F.sb * R.p1 + F.cb * w2 + (dc[2] + dk[2] * F.f);
+  real iq = (real)1 / q2;
+  x = u + F.f * q0 * iq;
+  y = v + F.f * q1 * fabs(iq);
+}
+
+// ptz_project_jac under the displaced model: d(x,y)/dq is formed from the displaced q, the rotation derivatives from
+// the rotated vector r (d does not turn with the camera), and the f column gains d(x,y)/dq * k.
+template <typename real>
+__device__ __forceinline__ void ptz_project_jac_disp(const FrameTab<real>& F, const RayTab<real>& R, real u, real v,
+                                                     const real (&dc)[3], const real (&dk)[3], real& x, real& y,
+                                                     real J[2][5]) {
+  const real D = (real)PTZ_D2R;
+  real w0 = F.ca * R.p0 - F.sa;
+  real w2 = F.sa * R.p0 + F.ca;
+  real r1 = F.cb * R.p1 + F.sb * w2;
+  real r2 = -F.sb * R.p1 + F.cb * w2;
+  real q0 = w0 + (dc[0] + dk[0] * F.f);
+  real q1 = r1 + (dc[1] + dk[1] * F.f);
+  real q2 = r2 + (dc[2] + dk[2] * F.f);
+  real iq = (real)1 / q2;
+  real iaq = fabs(iq);
+  real sg = q2 >= (real)0 ? (real)1 : (real)-1;
+  x = u + F.f * q0 * iq;
+  y = v + F.f * q1 * iaq;
+  // d(x,y)/dq
+  real fx = F.f * iq, fxz = -F.f * q0 * iq * iq;
+  real fy = F.f * iaq, fyz = -F.f * q1 * sg * iq * iq;
+  // dq/dpan = [-w2, sb w0, cb w0] D
+  real a0 = -w2 * D, a1 = F.sb * w0 * D, a2 = F.cb * w0 * D;
+  J[0][0] = fx * a0 + fxz * a2;
+  J[1][0] = fy * a1 + fyz * a2;
+  // dq/dtilt = [0, r2, -r1] D
+  J[0][1] = fxz * (-r1 * D);
+  J[1][1] = fy * (r2 * D) + fyz * (-r1 * D);
+  // d/df: the explicit f, and q's own dependence on f through d(f)
+  J[0][2] = q0 * iq + fx * dk[0] + fxz * dk[2];
+  J[1][2] = q1 * iaq + fy * dk[1] + fyz * dk[2];
+  // dq/dth = [ca d0, cb d1 + sb sa d0, -sb d1 + cb sa d0] D
+  real t0 = F.ca * R.d0t * D;
+  real t1 = (F.cb * R.d1t + F.sb * F.sa * R.d0t) * D;
+  real t2 = (-F.sb * R.d1t + F.cb * F.sa * R.d0t) * D;
+  J[0][3] = fx * t0 + fxz * t2;
+  J[1][3] = fy * t1 + fyz * t2;
+  // dq/dph = [0, cb e1, -sb e1] D
+  real e1 = F.cb * R.d1p * D, e2 = -F.sb * R.d1p * D;
+  J[0][4] = fxz * e2;
+  J[1][4] = fy * e1 + fyz * e2;
+}
+
 // ---------------------------------------------------------------- wave64 helpers
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

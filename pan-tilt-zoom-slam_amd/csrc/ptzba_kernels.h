@@ -75,6 +75,14 @@ __device__ __forceinline__ void slot_store9(real* p, const real (&x)[9]) {
   }
   p[8] = x[8];
 }
+// the displaced camera model's constants as a kernel argument (ptzba_common.h ptz_project_disp): d(f) = c + k f
+struct Disp6 {
+  double c[3], k[3];
+};
+// (disp6: the host's six doubles, nullptr: no displacement -- the launchers then run the kernels without it)
+inline Disp6 make_disp6(const double* disp6) {
+  return Disp6{{disp6[0], disp6[1], disp6[2]}, {disp6[3], disp6[4], disp6[5]}};
+}
 struct LinArgs {
   const int4* lm_work;           // [2 n_work] {landmark, s0, s1, first record}, {lm_meta}, heaviest first
   int n_work;
@@ -110,7 +118,27 @@ struct LinArgs {
   // reads its work descriptors (off the descriptor's latency), so a segment's frame table is an LDS read instead
   // of a global load that depends on the segment's frame id
   int n_pose;
+  // displaced model (ptzba_set_displacement): c = disp[0..2], k = disp[3..5] of d(f) = c + k f; read by the DISP
+  // instantiations only (the launchers pick them when `displaced`)
+  double disp[6];
+  float disp32[6];  // disp rounded to fp32 on the host: the fp32 instantiations' Jacobian constants (a thread owns one or
+                    // two segments, so six fp64 -> fp32 conversions per thread would show)
+  bool displaced;
 };
+// the displaced model's constants in the record precision (phase C)
+template <typename real>
+__device__ __forceinline__ void lin_disp(const LinArgs& a, real (&dc)[3], real (&dk)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if constexpr (sizeof(real) == 4) {
+      dc[k] = a.disp32[k];
+      dk[k] = a.disp32[3 + k];
+    } else {
+      dc[k] = a.disp[k];
+      dk[k] = a.disp[3 + k];
+    }
+  }
+}
 
 // K2 tiles: block of SCHUR_F1 consecutive free frames x chunk of 64 partner frames; work items are
 // splits of a tile's landmark list.  Static structure built once by ptzba_set_problem.
@@ -295,7 +323,7 @@ void launch_seg_row(const int32_t* seg_frame, const int32_t* frame_pos, int64_t 
 template <typename real>
 void launch_residual(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                      const void* rec_xy, const int64_t* perm, const void* ft64, const void* rt64, double u, double v,
-                     int64_t n_rec, double* r_out, hipStream_t st);
+                     const double* disp6, int64_t n_rec, double* r_out, hipStream_t st);
 
 // dense-tile SPD solve of the reduced camera system (chol_kernels.hip)
 // A: [ld][ld] row-major fp64, lower triangle of S in system order (n = n_aug rows incl. padding),
@@ -421,7 +449,8 @@ void launch_cov_joint(const CovArgs& z, const CovCrossArgs& x, hipStream_t st);
 template <typename real>
 void launch_cov_resid(const int32_t* rec_seg, const int32_t* seg_frame, const int32_t* seg_lm, const double2* seg_base,
                       const void* rec_xy, const void* rec_w, const void* ft64, const void* rt64, double u, double v,
-                      int64_t n_rec, int loss, double f_scale, double* part, int n_part, double* out, hipStream_t st);
+                      const double* disp6, int64_t n_rec, int loss, double f_scale, double* part, int n_part,
+                      double* out, hipStream_t st);
 
 // Gaussian pose priors (prior_kernels.hip; ptzba_set_pose_priors): factor k names G_k free frames, a mean and a
 // symmetric information matrix Lambda_k over their 3 G_k pose parameters; cost += 1/2 sum_k e_k^T Lambda_k e_k,

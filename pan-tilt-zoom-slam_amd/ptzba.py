@@ -194,6 +194,8 @@ def lib():
         "ptzba_pose_prior_info": ([V, V], I),
         "ptzba_set_ray_priors": ([V, POINTER(ptzba_ray_priors)], I),
         "ptzba_ray_prior_info": ([V, V], I),
+        "ptzba_set_displacement": ([V, V], I),
+        "ptzba_displacement_info": ([V, V], I),
         "ptzba_marginal_prior": ([V, POINTER(ptzba_marg_opts), V, I32, V, I64, I32, V, POINTER(c_int32), V, V, V,
                                  POINTER(c_double), POINTER(ptzba_marg_stats)], I),
         "ptzba_set_marginal_prior": ([V, POINTER(ptzba_marginal)], I),
@@ -307,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "ptz_keyframe_feature_counts", "ptz_match_sets_ransac", "ptz_pose_ransac", "ptzba_covariance",
     "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
     "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info", "ptzba_covariance_joint",
+    "ptzba_set_displacement", "ptzba_displacement_info",
     "ptzba_solver_buffers",
 ]
 
@@ -1665,6 +1668,24 @@ class BAHandle:
         _check(lib().ptzba_ray_prior_info(self.h, _ptr(out)), "ptzba_ray_prior_info")
         return int(out[0]), int(out[1]), int(out[2]), float(out[3])
 
+    def set_displacement(self, displacement):
+        """The projection-centre displacement (ptzba_set_displacement): six values lambda of the reference PTZCamera's
+        d(f) = (l0 + l3 f, l1 + l4 f, l2 + l5 f), a constant of the problem under which every projection of the handle
+        runs.  None or six zeros clears it.  Valid after set_problem, between solves; cleared by set_problem."""
+        if displacement is None:
+            return self.clear_displacement()
+        d = _f64(displacement, (6,))
+        _check(lib().ptzba_set_displacement(self.h, _ptr(d)), "ptzba_set_displacement")
+
+    def clear_displacement(self):
+        _check(lib().ptzba_set_displacement(self.h, None), "ptzba_set_displacement")
+
+    def displacement_info(self):
+        """(active, lambda[6]): whether a displacement is set, and its six values (zeros when none)."""
+        out = np.zeros(8)
+        _check(lib().ptzba_displacement_info(self.h, _ptr(out)), "ptzba_displacement_info")
+        return bool(out[0]), out[1:7].copy()
+
     def marginal_prior(self, drop_frames, drop_mask=None, pivot_tol=0.0, _struct_size=None):
         """ptzba_marginal_prior at the current state (a between-solves call): the Marginal that stands for the records
         of `drop_mask` (default: ptzba.drop_mask of the problem's frames, the pair form) and for every factor naming a
@@ -2174,7 +2195,7 @@ def _cov_kwargs(covariance):
 
 def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, weight=None, precision=FP64,
           loss=LOSS_LINEAR, f_scale=1.0, device=0, keep_handle=True, covariance=None, pose_priors=None,
-          marginal_prior=None, marginalize=None, ray_priors=None, **lm_kw):
+          marginal_prior=None, marginalize=None, ray_priors=None, displacement=None, **lm_kw):
     """Convenience one-shot solve.  Returns (ptz [N,3], rays [M,2], LMResult); with covariance= a dict of
     BAHandle.covariance's arguments (or True: every pose and ray block at unit scale) a fourth element, that call's
     (pose_cov, ray_cov, info) at the solution; an entry "joint": (frames, landmarks) in that dict adds
@@ -2187,8 +2208,16 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
     marginal_prior: a Marginal (BAHandle.set_marginal_prior; frame 0, the gauge, is conditioned at init_ptz[0]).
     marginalize: a list of leaving frames -- the last element of the result is then {"marginal": Marginal, "stats":
     dict}, BAHandle.marginal_prior(marginalize) at the solution.
-    ray_priors: a ray prior list [(landmark, mean, info), ...] (BAHandle.set_ray_priors), set after set_problem."""
+    ray_priors: a ray prior list [(landmark, mean, info), ...] (BAHandle.set_ray_priors), set after set_problem.
+    displacement: the camera's six projection-centre displacement values (BAHandle.set_displacement), set after
+    set_problem; None or zeros: the displacement-free model."""
     win = None
+    if displacement is not None:
+        displacement = _f64(displacement, (6,))
+        if not np.all(np.isfinite(displacement)):
+            raise ValueError("displacement: non-finite value")
+        if not np.any(displacement != 0):
+            displacement = None
     if ray_priors is not None:
         ray_priors = list(ray_priors)
         check_ray_priors(ray_priors, n_landmark)
@@ -2224,6 +2253,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                 h.set_pose_priors(pose_priors)
             if ray_priors:
                 h.set_ray_priors(ray_priors)
+            if displacement is not None:
+                h.set_displacement(displacement)
             h.set_state(init_ptz, init_rays)
             if marginal_prior is not None:
                 h.set_marginal_prior(marginal_prior)
@@ -2246,6 +2277,8 @@ def solve(n_pose, n_landmark, frame, landmark, xy, u, v, init_ptz, init_rays, we
                 h.set_pose_priors(pose_priors)
             if ray_priors:
                 h.set_ray_priors(ray_priors)
+            if displacement is not None:
+                h.set_displacement(displacement)
             t1 = time.perf_counter()
             h.set_state(init_ptz, init_rays)
             if marginal_prior is not None:

@@ -66,9 +66,14 @@ class Map:
     adjusted, older ones stay as they are (RandomForestMap's window rule, scene_map.py:198-244; the
     streaming config's 30-keyframe window).  marginalize=True (with a window): the matches of the keyframe a full
     window is about to lose are turned into a prior on the keyframes that stay (MarginalCarry) instead of being thrown
-    away."""
+    away.  ba_displacement: every bundle adjustment of the map runs under the camera's projection-centre displacement
+    (the one the tracker projects with), bundle_adjustment's displacement=.  Six values, or True: the `displacement`
+    attribute of the first keyframe that carries a non-zero one (read as PtzSlam._disp reads a camera's: all zero or
+    missing is none).  The map keeps the value once it has it -- the keyframes a bundle adjustment hands back are new
+    objects -- and copies it onto those keyframes."""
 
-    def __init__(self, feature_method, cache_correspondences=True, max_ba_frame=None, marginalize=False):
+    def __init__(self, feature_method, cache_correspondences=True, max_ba_frame=None, marginalize=False,
+                 ba_displacement=False):
         assert feature_method in ("sift", "orb", "latch")
         self.global_ray = np.ndarray([0, 2])
         self.keyframe_list = []
@@ -78,6 +83,30 @@ class Map:
         self.max_ba_frame = max_ba_frame
         self.correspondences = CorrespondenceCache() if cache_correspondences else None
         self.marginal_carry = MarginalCarry() if marginalize and max_ba_frame else None
+        self.ba_displacement = None  # the six values, once known
+        self._ba_displacement_from_keyframes = ba_displacement is True
+        if ba_displacement is not True and ba_displacement is not False and ba_displacement is not None:
+            self.ba_displacement = self._nonzero6(ba_displacement)
+            if self.ba_displacement is None:
+                raise ValueError("ba_displacement: six finite values, not all zero, expected (or True / False)")
+
+    @staticmethod
+    def _nonzero6(d):
+        """d as six float64 values, or None when it is missing, malformed or all zero."""
+        if d is None:
+            return None
+        d = np.asarray(d, np.float64).reshape(-1)
+        return d.copy() if d.shape == (6,) and np.isfinite(d).all() and np.any(d != 0) else None
+
+    def _displacement_for_ba(self, keyframes):
+        """The displacement of the next bundle adjustment (None: none); with ba_displacement=True it is looked for on
+        the given keyframes until one carries it."""
+        if self.ba_displacement is None and self._ba_displacement_from_keyframes:
+            for k in keyframes:
+                self.ba_displacement = self._nonzero6(getattr(k, "displacement", None))
+                if self.ba_displacement is not None:
+                    break
+        return self.ba_displacement
 
     def add_first_keyframe(self, keyframe, verbose=False):
         assert isinstance(keyframe, KeyFrame)
@@ -125,6 +154,9 @@ class Map:
             if n == self.max_ba_frame:
                 leaving = image_indices[0]
                 prior_kw["marginalize"] = [leaving]
+        disp = self._displacement_for_ba([ref] + self.keyframe_list)
+        if disp is not None:
+            prior_kw["displacement"] = disp.copy()
         start = time.time()
         out = bundle_adjustment(images, image_indices, self.feature_method, initial_ptzs, ref.center,
                                 ref.base_rotation, ref.u, ref.v, save_path, verbose,
@@ -137,6 +169,8 @@ class Map:
         self.global_ray = landmarks
         self.keyframe_list = list(kept)
         for i, kf in enumerate(keyframes):
+            if disp is not None:
+                kf.displacement = disp.copy()
             if kf.has_features():  # (get_feature_num() > 0 without forming the lists: they are formed on first use)
                 self.keyframe_list.append(kf)
             else:
