@@ -23,13 +23,7 @@
 // Jacobian (they depend on pose and ray only), so the Jacobian and the 3x3/3x2/2x2 normal-equation
 // blocks are formed once per segment.
 #include "../../include/ptzba.h"
-#include "ptzba_common.h"
-#include <hip/hip_ext.h>
-
-#include "ptzba_kernels.h"
-#include "robust_loss.h"
-
-#include <type_traits>
+#include "k1_device.h"
 
 namespace ptzba {
 
@@ -79,9 +73,6 @@ void launch_tables(const double* ptz, const double* rays, int n_pose, int n_lm, 
 // K1: linearize (residual + Jacobian + per-segment / per-landmark normal-equation blocks + cost)
 // ------------------------------------------------------------------------------------------------
 constexpr int SEGW = K1_SEGW;  // segments per LDS window per wave
-#ifndef K1_FTL_ALWAYS
-#define K1_FTL_ALWAYS 1
-#endif
 #ifndef K1_RPL
 #define K1_RPL 4  // phase B: records per lane (one segmented scan per 64 K1_RPL records; 8 measured 62.0 vs 60.4 us, r06j)
 #endif
@@ -94,58 +85,6 @@ constexpr int SEGW = K1_SEGW;  // segments per LDS window per wave
 #ifndef K1_MIN_WAVES64
 #define K1_MIN_WAVES64 3  // fp64: 4 waves/SIMD spill 128-196 B/lane; 3 fit (fp64 K1 193 -> 138 us, r02 A/B)
 #endif
-
-// ---- DPP lane shuffles (VALU, no LDS round trip).  Lanes whose source is out of range or whose row
-// is masked off read 0 (bound_ctrl), which the segmented scan treats as "different segment".
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ int dpp_i(int x) {
-  return __builtin_amdgcn_update_dpp(0, x, CTRL, ROWMASK, 0xf, true);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float dpp_r(float x) {
-  return __int_as_float(dpp_i<CTRL, ROWMASK>(__float_as_int(x)));
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_r(double x) {
-  const int lo = dpp_i<CTRL, ROWMASK>(__double2loint(x)), hi = dpp_i<CTRL, ROWMASK>(__double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;
-constexpr int DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143, DPP_WAVE_SHL1 = 0x130;
-
-// Wave total by a DPP inclusive scan (VALU only): the sum is valid in lane 63.  Needs every lane active.
-// The butterfly of wave_sum costs one LDS round trip (ds_bpermute) per step and value: at the end of K1
-// six fp64 butterflies took ~5K cycles per wave, 15 % of the wave's time (K1_TIMING build).
-template <typename T>
-__device__ __forceinline__ T wave_total(T v) {
-  v += dpp_r<DPP_ROW_SHR1, 0xf>(v);
-  v += dpp_r<DPP_ROW_SHR2, 0xf>(v);
-  v += dpp_r<DPP_ROW_SHR4, 0xf>(v);
-  v += dpp_r<DPP_ROW_SHR8, 0xf>(v);
-  v += dpp_r<DPP_ROW_BCAST15, 0xa>(v);
-  v += dpp_r<DPP_ROW_BCAST31, 0xc>(v);
-  return v;
-}
-
-// Six wave totals at once, step by step across the values (round 6): each DPP step's six reads of the previous step's
-// results are independent, so the DPP read-after-write wait states of one value are covered by the others' work
-// instead of s_nop padding (six back-to-back wave_total calls serialised).  Same additions, same order per value.
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ void wave_total_step6(double (&v)[6]) {
-  double t[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) t[k] = dpp_r<CTRL, ROWMASK>(v[k]);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v[k] += t[k];
-}
-__device__ __forceinline__ void wave_total6(double (&v)[6]) {
-  wave_total_step6<DPP_ROW_SHR1, 0xf>(v);
-  wave_total_step6<DPP_ROW_SHR2, 0xf>(v);
-  wave_total_step6<DPP_ROW_SHR4, 0xf>(v);
-  wave_total_step6<DPP_ROW_SHR8, 0xf>(v);
-  wave_total_step6<DPP_ROW_BCAST15, 0xa>(v);
-  wave_total_step6<DPP_ROW_BCAST31, 0xc>(v);
-}
 
 // one Kogge-Stone step of the segmented inclusive scan (keys sorted within the wave; kenc >= 1)
 template <int CTRL, int ROWMASK, typename real>
@@ -176,26 +115,22 @@ __device__ long long g_k1_items[32768][8];  // start, end, A, B, C, final, segme
 #define K1_NOW(t) do { } while (0)
 #define K1_ACC(k, t0, t1) do { } while (0)
 #endif
-// FTL: the frame tables are staged in LDS (n_pose <= K1_FT_LDS): phase A's chain is descriptor -> segment frame id
-// -> LDS instead of descriptor -> frame id -> global frame table (one dependent memory latency less per wave)
+// The workgroup's frame range of the frame tables is staged in LDS (k1_device.h): phase A's chain is descriptor ->
+// segment frame id -> LDS instead of descriptor -> frame id -> global frame table (one dependent memory latency less
+// per wave); a workgroup whose range exceeds the table reads the tables from global memory
 // WT: records carry multiplicities (rec_w; the dedup form) -- unweighted problems keep no weight registers
 // DISP: the displaced camera model (ptzba_common.h ptz_project_disp; LinArgs::disp) in phase A's projection and phase
-// C's Jacobian; the other instantiations compile the source they always did.  LDS-table form only: it serves any
-// n_pose (a workgroup whose frame range exceeds the table reads global memory), the global-table form is an A/B build
-template <typename real, int LOSS, bool FTL, bool WT = true, bool DISP = false>
+// C's Jacobian
+template <typename real, int LOSS, bool WT, bool DISP>
 __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_MIN_WAVES64) void k_linearize(LinArgs a) {
-  static_assert(FTL || !DISP, "the displaced model is instantiated for the LDS-table form only");
   __shared__ real s_x[K1_WPB][SEGW], s_y[K1_WPB][SEGW], s_acc[K1_WPB][4][SEGW];
-  __shared__ double s_ft[5][FTL ? K1_FT_LDS : 1];  // ca, sa, cb, sb, f per frame (fp64)
+  __shared__ K1FrameLds s_ft;
   const int lane = lane_id();
   // wave-uniform by construction: with readfirstlane the compiler sees it, so the descriptor, the ray table, the
   // window and record bounds and the slot offsets are scalar loads / SGPRs (SALU address math, fewer VGPRs)
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int task = blockIdx.x * K1_WPB + wv;
   if (a.run_if && !*a.run_if) return;  // conditional re-linearisation (device-driven LM): the whole grid leaves
-  if constexpr (!FTL) {
-    if (task >= a.n_work) return;  // whole wave leaves; no block-level barriers in this variant
-  }
   long long kt0 = 0, kt1 = 0, kt2 = 0, kt3 = 0, kt4 = 0, k1acc[4] = {0, 0, 0, 0};
   (void)kt0; (void)kt1; (void)kt2; (void)kt3; (void)kt4; (void)k1acc;
   K1_NOW(kt0);
@@ -205,35 +140,13 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
   // one 32-B work descriptor {landmark, first segment, end segment, first record | first frame, last
   // frame, slot offset, end record of the first window}: no dependent lm_order -> lm_seg_begin -> seg_rec_begin -> lm_meta chain before
   // the records and the frame tables can be requested
-  const int tq = FTL ? min(task, a.n_work - 1) : task;
+  const int tq = min(task, a.n_work - 1);
   const int4 wd = a.lm_work[2 * tq];
   const int4 wm = a.lm_work[2 * tq + 1];
-  int fbase = 0;  // FTL: the first staged frame (s_ft[k][fs - fbase])
-  bool ftl_ok = FTL;  // FTL: this workgroup's frame range fits the LDS table
-  if constexpr (FTL) {
-    // the frames the workgroup's landmarks see, [min first frame, max last frame] over its K1_WPB descriptors (scalar
-    // loads; the work order keeps a workgroup's landmarks close in frame order, so this is ~a coupling window, not the
-    // whole table); the barrier below is the block's only one
-    int fmax = -1;
-    fbase = a.n_pose;
-#pragma unroll
-    for (int q = 0; q < K1_WPB; ++q) {
-      const int4 m = a.lm_work[2 * min((int)blockIdx.x * K1_WPB + q, a.n_work - 1) + 1];
-      fbase = min(fbase, m.x);
-      fmax = max(fmax, m.y);
-    }
-    ftl_ok = k1_ftl_fits(fbase, fmax);  // (else this workgroup reads the tables from global memory)
-    const double4* src = reinterpret_cast<const double4*>(a.ft64);
-    if (ftl_ok)
-    for (int e = fbase + (int)threadIdx.x; e <= fmax; e += blockDim.x) {
-      const double4 t0 = src[2 * e];
-      const double f = reinterpret_cast<const double*>(a.ft64)[8 * e + 4];
-      const int el = e - fbase;
-      s_ft[0][el] = t0.x; s_ft[1][el] = t0.y; s_ft[2][el] = t0.z; s_ft[3][el] = t0.w; s_ft[4][el] = f;
-    }
-    __syncthreads();
-    if (task >= a.n_work) return;  // whole wave leaves after the barrier
-  }
+  int fbase;                                            // the first staged frame (s_ft[k][fs - fbase])
+  const bool ftl_ok = k1_stage_frames(a, s_ft, fbase);  // this workgroup's frame range fits the LDS table
+  __syncthreads();                                      // the block's only barrier
+  if (task >= a.n_work) return;                         // whole wave leaves after the barrier
   auto ft_lds = [&](int fs) {
     if (!ftl_ok) return ((const FrameTab<double>*)a.ft64)[fs];
     FrameTab<double> F;
@@ -243,7 +156,6 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
     return F;
   };
   const int l = wd.x, s0 = wd.y, s1 = wd.z;
-  const FrameTab<double>* __restrict__ ft64 = (const FrameTab<double>*)a.ft64;
   const RayTab<double> R64 = ((const RayTab<double>*)a.rt64)[l];
   RayTab<real> R;  // the record-precision table is the rounded fp64 one (k_tables)
   R.p0 = (real)R64.p0; R.p1 = (real)R64.p1; R.d0t = (real)R64.d0t; R.d1t = (real)R64.d1t; R.d1p = (real)R64.d1p;
@@ -407,9 +319,8 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
     load_cgrp(ca, rb0, r1);
     // phase A: fp64 projection of every segment of the window (lanes over segments), kept as the
     // offset from the segment's base observation so phase B works on O(residual) magnitudes.  The
-    // frame ids and the phase-C frame tables stay in registers.
+    // frame ids stay in registers for phase C.
     int fsv[SEGW / WAVE];
-    FrameTab<real> ftv[SEGW / WAVE];  // phase C's frame tables, loaded here (off phase C's path)
 #pragma unroll
     for (int i = 0; i < SEGW / WAVE; ++i) {
       const int s = w0 + lane + i * WAVE;
@@ -419,20 +330,11 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
         const int fs = a.seg_frame[s];
         fsv[i] = fs;
         double x, y;
-        if constexpr (DISP) {
-          const double dc[3] = {a.disp[0], a.disp[1], a.disp[2]}, dk[3] = {a.disp[3], a.disp[4], a.disp[5]};
-          ptz_project_disp<double>(ft_lds(fs), R64, a.u, a.v, dc, dk, x, y);  // (LDS, or global when !ftl_ok)
-        } else if constexpr (FTL) ptz_project<double>(ft_lds(fs), R64, a.u, a.v, x, y);
-        else ptz_project<double>(ft64[fs], R64, a.u, a.v, x, y);
+        k1_project64<DISP>(a, ft_lds(fs), R64, x, y);
         const double2 bs = seg_base[s];
         sx[sl] = (real)(x - bs.x);
         sy[sl] = (real)(y - bs.y);
         acc0[sl] = 0; acc1[sl] = 0; acc2[sl] = 0; acc3[sl] = 0;
-      }
-      if constexpr (!FTL) {  // (FTL: phase C reads its tables from LDS)
-        // the five used fields only (not the 32-B struct)
-        const FrameTab<real>* fp = ft + fsv[i];
-        ftv[i].ca = fp->ca; ftv[i].sa = fp->sa; ftv[i].cb = fp->cb; ftv[i].sb = fp->sb; ftv[i].f = fp->f;
       }
     }
     wave_lds_fence();
@@ -474,9 +376,9 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
           F.pad0 = F.pad1 = F.pad2 = (real)0;
         }
         ptz_project_jac_disp<real>(F, R, u, v, dc, dk, x, y, J);
-      } else if (FTL && !ftl_ok) {
+      } else if (!ftl_ok) {
         ptz_project_jac<real>(ft[fs], R, u, v, x, y, J);
-      } else if constexpr (FTL) {
+      } else {
         // the record-precision table is the rounded fp64 one (k_tables): the same values as ft[fs]
         FrameTab<real> F;
         const int fl = fs - fbase;
@@ -484,8 +386,6 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
         F.f = (real)s_ft[4][fl];
         F.pad0 = F.pad1 = F.pad2 = (real)0;
         ptz_project_jac<real>(F, R, u, v, x, y, J);
-      } else {
-        ptz_project_jac<real>(ftv[i], R, u, v, x, y, J);
       }
       const real Sx = acc0[sl], Sy = acc1[sl], Srx = acc2[sl], Sry = acc3[sl];
       // W = Jp^T diag(Sx,Sy) Jr (3x2), U = Jp^T diag Jp (upper: 00 01 02 11 12 22), g_pose = Jp^T (w r)
@@ -515,13 +415,8 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
     K1_ACC(2, kt2, kt3);
     kt0 = kt3;
   }
-  double tot[6] = {V00, V01, V11, g0, g1, cost};
-  wave_total6(tot);
-  V00 = tot[0]; V01 = tot[1]; V11 = tot[2]; g0 = tot[3]; g1 = tot[4]; cost = tot[5];
-  if (lane == WAVE - 1) {
-    double* o = (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8;
-    o[0] = V00; o[1] = V01; o[2] = V11; o[3] = g0; o[4] = g1; o[5] = 0.5 * cost; o[6] = 0; o[7] = 0;
-  }
+  double lm[6] = {V00, V01, V11, g0, g1, cost};
+  k1_store_landmark(lm, (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8);
 #ifdef K1_TIMING
   K1_NOW(kt4);
   K1_ACC(3, kt3, kt4);
@@ -533,34 +428,19 @@ __global__ __launch_bounds__(64 * K1_WPB, sizeof(real) == 4 ? K1_MIN_WAVES : K1_
 #endif
 }
 
+// one instantiation per precision, loss (the template value is the PTZBA_LOSS_* id), weight form and camera model.
+// The frame tables are staged in LDS per workgroup frame range for any n_pose; a workgroup whose range exceeds
+// K1_FT_LDS frames reads them from global memory (config 4's multi-row landmarks)
 template <typename real>
 void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  if (a.n_work <= 0) return;
-  dim3 grid((a.n_work + K1_WPB - 1) / K1_WPB);
-  // frame tables staged in LDS per workgroup frame range (round 6: any n_pose; a workgroup whose range exceeds K1_FT_LDS
-  // frames reads them from global memory -- config 4's multi-row landmarks); the global-table form stays for A/B builds
-  const bool ftl = K1_FTL_ALWAYS ? true : a.n_pose <= K1_FT_LDS;
-  auto go = [&](auto kern) {
-    if (ev0) hipExtLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, ev0, ev1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, a);
-  };
-  const bool wt = a.rec_w != nullptr;
-  // one instantiation per loss (the template value is the PTZBA_LOSS_* id), frame-table path and weight form
-  // (the displaced model: the LDS-table form only, which serves any n_pose -- one extra instantiation per loss and
-  // weight form, not two)
-  auto pick = [&](auto loss_c) {
-    constexpr int L = decltype(loss_c)::value;
-    if (a.displaced) wt ? go(k_linearize<real, L, true, true, true>) : go(k_linearize<real, L, true, false, true>);
-    else if (ftl) wt ? go(k_linearize<real, L, true, true>) : go(k_linearize<real, L, true, false>);
-    else wt ? go(k_linearize<real, L, false, true>) : go(k_linearize<real, L, false, false>);
-  };
-  switch (loss) {
-    case PTZBA_LOSS_LINEAR: pick(std::integral_constant<int, PTZBA_LOSS_LINEAR>{}); break;
-    case PTZBA_LOSS_HUBER: pick(std::integral_constant<int, PTZBA_LOSS_HUBER>{}); break;
-    case PTZBA_LOSS_SOFT_L1: pick(std::integral_constant<int, PTZBA_LOSS_SOFT_L1>{}); break;
-    case PTZBA_LOSS_CAUCHY: pick(std::integral_constant<int, PTZBA_LOSS_CAUCHY>{}); break;
-    default: pick(std::integral_constant<int, PTZBA_LOSS_ARCTAN>{}); break;  // (ptzba_set_problem refuses other ids)
-  }
+  k1_with_loss(loss, [&](auto loss_c) {
+    k1_with_flag(a.rec_w != nullptr, [&](auto wt_c) {
+      k1_with_flag(a.displaced, [&](auto disp_c) {
+        k1_launch(k_linearize<real, decltype(loss_c)::value, decltype(wt_c)::value, decltype(disp_c)::value>, a, st, ev0,
+                  ev1);
+      });
+    });
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

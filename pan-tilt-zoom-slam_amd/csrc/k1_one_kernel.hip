@@ -2,54 +2,24 @@
 // repeats are all adjacent -- config 3, the reference's pipeline): `k_linearize_one`.
 //
 // Same work split, tables, outputs and arithmetic per record as k_linearize (ba_kernels.hip): one wave per landmark,
-// K1_WPB landmarks per workgroup, the workgroup's frame range of the fp64 frame tables staged in LDS (global-table
-// fallback when the range exceeds K1_FT_LDS).  What is gone is phase B: segment s of the landmark owns record
-// r0 + (s - s0), so the lane that projects the segment loads that record, forms its residual, robust weights and cost
-// term and goes straight on to the segment's Jacobian and normal-equation blocks -- no key stream, no 4-record groups,
-// no segmented scan, no LDS sums, no CSR load for later windows.  A kernel of its own, in its own translation unit:
-// as a fifth form of the k_linearize template it changed how hipcc compiled the other forms.
+// K1_WPB landmarks per workgroup, the workgroup's frame range of the fp64 frame tables staged in LDS (a workgroup whose
+// range exceeds K1_FT_LDS reads them from global memory).  What is gone is phase B: segment s of the landmark owns
+// record r0 + (s - s0), so the lane that projects the segment loads that record, forms its residual, robust weights and
+// cost term and goes straight on to the segment's Jacobian and normal-equation blocks -- no key stream, no 4-record
+// groups, no segmented scan, no LDS sums, no CSR load for later windows.  A kernel of its own, in its own translation
+// unit: as a further form of the k_linearize template it changed how hipcc compiled the other forms.  The
+// frame staging, the fp64 projection, the wave totals and the launch dispatch are k_linearize's own (k1_device.h).
 #include "../../include/ptzba.h"
-#include "ptzba_common.h"
-#include <hip/hip_ext.h>
-
-#include "ptzba_kernels.h"
-#include "robust_loss.h"
-
-#include <type_traits>
+#include "k1_device.h"
 
 namespace ptzba {
 
 namespace {
 
-// wave totals of six doubles by a DPP inclusive scan, valid in lane 63 (ba_kernels.hip wave_total6: the same
-// additions in the same order)
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_d(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ void total_step6(double (&v)[6]) {
-  double t[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) t[k] = dpp_d<CTRL, ROWMASK>(v[k]);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v[k] += t[k];
-}
-__device__ __forceinline__ void total6(double (&v)[6]) {
-  total_step6<0x111, 0xf>(v);  // row_shr 1, 2, 4, 8
-  total_step6<0x112, 0xf>(v);
-  total_step6<0x114, 0xf>(v);
-  total_step6<0x118, 0xf>(v);
-  total_step6<0x142, 0xa>(v);  // row_bcast 15, 31
-  total_step6<0x143, 0xc>(v);
-}
-
 // DISP: the displaced camera model (ptzba_common.h; LinArgs::disp) in the fp64 projection and in the Jacobian
-template <typename real, int LOSS, bool DISP = false>
+template <typename real, int LOSS, bool DISP>
 __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
-  __shared__ double s_ft[5][K1_FT_LDS];  // ca, sa, cb, sb, f per staged frame (fp64)
+  __shared__ K1FrameLds s_ft;
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int task = blockIdx.x * K1_WPB + wv;
@@ -57,24 +27,10 @@ __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
   const int tq = min(task, a.n_work - 1);
   const int4 wd = a.lm_work[2 * tq];      // {landmark, first segment, end segment, first record}
   const int4 wm = a.lm_work[2 * tq + 1];  // {first frame, last frame, slot offset, -}
-  // the frames the workgroup's landmarks see; the barrier below is the block's only one
-  int fmax = -1, fbase = a.n_pose;
-#pragma unroll
-  for (int q = 0; q < K1_WPB; ++q) {
-    const int4 m = a.lm_work[2 * min((int)blockIdx.x * K1_WPB + q, a.n_work - 1) + 1];
-    fbase = min(fbase, m.x);
-    fmax = max(fmax, m.y);
-  }
-  const bool ftl_ok = k1_ftl_fits(fbase, fmax);  // (else this workgroup reads the tables from global memory)
-  if (ftl_ok)
-    for (int e = fbase + (int)threadIdx.x; e <= fmax; e += blockDim.x) {
-      const double4 t0 = reinterpret_cast<const double4*>(a.ft64)[2 * e];
-      const double f = reinterpret_cast<const double*>(a.ft64)[8 * e + 4];
-      const int el = e - fbase;
-      s_ft[0][el] = t0.x; s_ft[1][el] = t0.y; s_ft[2][el] = t0.z; s_ft[3][el] = t0.w; s_ft[4][el] = f;
-    }
-  __syncthreads();
-  if (task >= a.n_work) return;  // whole wave leaves after the barrier
+  int fbase;                              // the first staged frame
+  const bool ftl_ok = k1_stage_frames(a, s_ft, fbase);  // (else this workgroup reads the tables from global memory)
+  __syncthreads();                                       // the block's only barrier
+  if (task >= a.n_work) return;                          // whole wave leaves after the barrier
 
   const int l = wd.x, s0 = wd.y, s1 = wd.z;
   const RayTab<double> R64 = ((const RayTab<double>*)a.rt64)[l];
@@ -115,12 +71,7 @@ __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
       F64 = ((const FrameTab<double>*)a.ft64)[fs];
     }
     double x64, y64;
-    if constexpr (DISP) {
-      const double dc[3] = {a.disp[0], a.disp[1], a.disp[2]}, dk[3] = {a.disp[3], a.disp[4], a.disp[5]};
-      ptz_project_disp<double>(F64, R64, a.u, a.v, dc, dk, x64, y64);
-    } else {
-      ptz_project<double>(F64, R64, a.u, a.v, x64, y64);
-    }
+    k1_project64<DISP>(a, F64, R64, x64, y64);
     const double2 bs = a.seg_base[s];
     const real rx = (real)(x64 - bs.x) - ox, ry = (real)(y64 - bs.y) - oy;
     // the record's robust terms (k_linearize's consume_c): gradient weights wx, wy = w rho', Hessian weights hx, hy
@@ -197,41 +148,19 @@ __global__ __launch_bounds__(64 * K1_WPB, 4) void k_linearize_one(LinArgs a) {
     g1 += (double)(J[0][4] * Srx + J[1][4] * Sry);
   }
   // (the loop's trip count differs per lane: every lane is active again here, as the DPP totals need)
-  double tot[6] = {V00, V01, V11, g0, g1, cost};
-  total6(tot);
-  if (lane == WAVE - 1) {
-    double* o = (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8;
-    o[0] = tot[0]; o[1] = tot[1]; o[2] = tot[2]; o[3] = tot[3]; o[4] = tot[4]; o[5] = 0.5 * tot[5]; o[6] = 0; o[7] = 0;
-  }
+  double lm[6] = {V00, V01, V11, g0, g1, cost};
+  k1_store_landmark(lm, (alt ? a.lm_out1 : a.lm_out) + (int64_t)l * 8);
 }
 
 }  // namespace
 
 template <typename real>
 void launch_linearize_one(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  if (a.n_work <= 0) return;
-  dim3 grid((a.n_work + K1_WPB - 1) / K1_WPB);
-  auto go = [&](auto kern) {
-    if (ev0) hipExtLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, ev0, ev1, 0, a);
-    else hipLaunchKernelGGL(kern, grid, dim3(64 * K1_WPB), 0, st, a);
-  };
-  if (a.displaced) {
-    switch (loss) {
-      case PTZBA_LOSS_LINEAR: go(k_linearize_one<real, PTZBA_LOSS_LINEAR, true>); break;
-      case PTZBA_LOSS_HUBER: go(k_linearize_one<real, PTZBA_LOSS_HUBER, true>); break;
-      case PTZBA_LOSS_SOFT_L1: go(k_linearize_one<real, PTZBA_LOSS_SOFT_L1, true>); break;
-      case PTZBA_LOSS_CAUCHY: go(k_linearize_one<real, PTZBA_LOSS_CAUCHY, true>); break;
-      default: go(k_linearize_one<real, PTZBA_LOSS_ARCTAN, true>); break;
-    }
-    return;
-  }
-  switch (loss) {
-    case PTZBA_LOSS_LINEAR: go(k_linearize_one<real, PTZBA_LOSS_LINEAR>); break;
-    case PTZBA_LOSS_HUBER: go(k_linearize_one<real, PTZBA_LOSS_HUBER>); break;
-    case PTZBA_LOSS_SOFT_L1: go(k_linearize_one<real, PTZBA_LOSS_SOFT_L1>); break;
-    case PTZBA_LOSS_CAUCHY: go(k_linearize_one<real, PTZBA_LOSS_CAUCHY>); break;
-    default: go(k_linearize_one<real, PTZBA_LOSS_ARCTAN>); break;  // (ptzba_set_problem refuses other ids)
-  }
+  k1_with_loss(loss, [&](auto loss_c) {
+    k1_with_flag(a.displaced, [&](auto disp_c) {
+      k1_launch(k_linearize_one<real, decltype(loss_c)::value, decltype(disp_c)::value>, a, st, ev0, ev1);
+    });
+  });
 }
 
 template void launch_linearize_one<float>(const LinArgs&, int, hipStream_t, hipEvent_t, hipEvent_t);

@@ -391,7 +391,7 @@ void layout_k1_order(ProblemLayout& L, int n_pose, int n_lm) {
   {
     // heaviest first (LPT over the workgroup slots) at 1/8-octave resolution of the record count, and inside such a
     // size class by first frame: a K1 workgroup's landmarks then see neighbouring frames, so it stages ~a coupling
-    // window of frame tables instead of the whole table (ba_kernels.hip FTL)
+    // window of frame tables instead of the whole table (k1_device.h k1_stage_frames)
     auto nrec = [&](int l) { return k1_rec_begin[lm_seg_begin[l + 1]] - k1_rec_begin[lm_seg_begin[l]]; };
     auto size_class = [&](int l) {
       const uint64_t c = (uint64_t)nrec(l);

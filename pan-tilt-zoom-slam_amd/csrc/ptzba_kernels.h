@@ -10,8 +10,9 @@ constexpr int K1_SEGW = 128;  // K1 segments per LDS window per wave
 #define K1_FT_LDS_N 384
 #endif
 // K1 stages its workgroup's frame range of the frame tables in LDS (5 x 8 B per frame) when the range holds at most this
-// many frames, else the workgroup reads them from global memory.  Round 6: 640 -> 384 frames (15 KB instead of 25 KB),
-// so five workgroups of four waves fit a CU's LDS (38 -> 27 KB per workgroup): 5 waves / SIMD instead of 4
+// many frames, else the workgroup reads them from global memory (a per-workgroup fallback inside the one form of each
+// kernel: there is no global-table build of K1).  Round 6: 640 -> 384 frames (15 KB instead of 25 KB), so five
+// workgroups of four waves fit a CU's LDS (38 -> 27 KB per workgroup): 5 waves / SIMD instead of 4
 constexpr int K1_FT_LDS = K1_FT_LDS_N;
 #ifndef K1_WPB
 #define K1_WPB 4  // waves (landmarks) per workgroup: the frame tables are staged once per workgroup
@@ -114,9 +115,9 @@ struct LinArgs {
   double* lm_out1;
   const int* sel;
   int sel_xor;
-  // frames of the problem: with n_pose <= K1_FT_LDS every workgroup stages the fp64 frame tables in LDS before it
-  // reads its work descriptors (off the descriptor's latency), so a segment's frame table is an LDS read instead
-  // of a global load that depends on the segment's frame id
+  // frames of the problem (k1_stage_frames starts its minimum from it): every workgroup stages its own frame range of
+  // the fp64 frame tables in LDS when k1_ftl_fits, so a segment's frame table is an LDS read instead of a global load
+  // that depends on the segment's frame id
   int n_pose;
   // displaced model (ptzba_set_displacement): c = disp[0..2], k = disp[3..5] of d(f) = c + k f; read by the DISP
   // instantiations only (the launchers pick them when `displaced`)

@@ -131,17 +131,20 @@ def _crafted(kind):
     LDS-table kernels, landmarks walked in four segment windows -- under LAMBDA.  The observations move by
     proj_LAMBDA(x0) - proj_0(x0), so the residuals at x0 stay what k1_cases made them and only the Jacobian tells the
     two models apart.  kind: "general" (k_linearize, unweighted), "weighted" (integer multiplicities), "one_record"
-    (the first record of every segment, twice: merged to one record per segment, k_linearize_one).  Returns
+    (the first record of every segment, twice: merged to one record per segment, k_linearize_one);
+    "one_record_plain": the same with the observations left where k1_cases put them (a problem of the displacement-free
+    model).  Returns
     (problem for the handle, weight, reference step under LAMBDA, displacement-free reference step)."""
     import types
     import k1_cases as kc
     u, v, ptz0, rays0, frame, landmark, xy, weight = kc.craft(weighted=kind == "weighted")
-    if kind == "one_record":
+    if kind.startswith("one_record"):
         _, first = np.unique(landmark.astype(np.int64) * len(ptz0) + frame, return_index=True)
         first = np.sort(first)
         frame, landmark, xy = np.repeat(frame[first], 2), np.repeat(landmark[first], 2), np.repeat(xy[first], 2, axis=0)
-    xy = xy + (disp_ref.project(u, v, ptz0[frame], rays0[landmark], LAMBDA)[0] -
-               disp_ref.project(u, v, ptz0[frame], rays0[landmark], ZERO)[0])
+    if not kind.endswith("_plain"):
+        xy = xy + (disp_ref.project(u, v, ptz0[frame], rays0[landmark], LAMBDA)[0] -
+                   disp_ref.project(u, v, ptz0[frame], rays0[landmark], ZERO)[0])
     p = types.SimpleNamespace(n_pose=len(ptz0), n_landmark=len(rays0), frame=frame, landmark=landmark, xy=xy, u=u, v=v,
                               init_ptz=ptz0, init_rays=rays0)
     k = np.ones(len(frame), np.int64) if weight is None else weight.astype(np.int64)
@@ -149,7 +152,35 @@ def _crafted(kind):
                                     "xy": np.repeat(xy, k, axis=0)})  # every record repeated `weight` times
     dx1 = disp_ref.gn_step(full, ptz0, rays0, LAMBDA)[0]
     dx0 = disp_ref.gn_step(full, ptz0, rays0, ZERO)[0]
+    _crafted_full[kind] = full
     return p, weight, _frozen(dx1), _frozen(dx0)
+
+
+_crafted_full = {}  # kind -> the expanded records of _crafted(kind), for the robust reference below
+
+
+@functools.lru_cache(maxsize=None)
+def _crafted_lin(kind, lam_key):
+    """(J, r) of _crafted(kind)'s expanded records at x0 under LAMBDA ("disp") or without a displacement ("plain")."""
+    _crafted(kind)
+    full = _crafted_full[kind]
+    lam = LAMBDA if lam_key == "disp" else ZERO
+    return (disp_ref.jacobian(full, full.init_ptz, full.init_rays, lam),
+            _frozen(disp_ref.residual(full, full.init_ptz, full.init_rays, lam)))
+
+
+@functools.lru_cache(maxsize=None)
+def _crafted_robust_step(kind, loss, hcurv, lam_key):
+    """One undamped step of the robust cost on _crafted(kind): disp_ref's displaced Jacobian and residual with
+    loss_ref.weights' gradient weight w1 = rho' and curvature weight w2 = max(rho' + 2 z rho'', hcurv rho') (huber:
+    hcurv rho' beyond the unit), f_scale 1 as _handle sets it: (J^T diag(w2) J) dx = -J^T (w1 r)."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spla
+    import loss_ref
+    J, r = _crafted_lin(kind, lam_key)
+    _, _, w1, w2 = loss_ref.weights(r, loss, hcurv, 1.0)
+    H = (J.T @ sp.diags(w2) @ J).tocsc()
+    return _frozen(spla.spsolve(H, -np.asarray(J.T @ (w1 * r)).reshape(-1)))
 
 
 @pytest.mark.parametrize("kind", ["general", "weighted", "one_record"])
@@ -171,6 +202,60 @@ def test_global_table_fallback_takes_the_displaced_path(gpu_available, precision
     err = _step_err(dx_gpu, dx)
     print(f"crafted {kind} precision {precision}: step error {err:.3e} (tol {tol:.0e}); displacement-free step "
           f"{moved:.3e} away; k1_info {info}; {merge}")
+    assert err < tol, err
+
+
+@pytest.mark.parametrize("loss", ["huber", "soft_l1", "cauchy", "arctan"])
+@pytest.mark.parametrize("kind", ["general", "weighted", "one_record"])
+@pytest.mark.parametrize("precision", [0, 1])
+def test_robust_losses_take_the_displaced_path_on_both_table_paths(gpu_available, precision, kind, loss):
+    """The displaced instantiations of k_linearize (unweighted, weighted) and k_linearize_one under each robust loss,
+    with workgroups on the LDS table and on the `!ftl_ok` fallback in one launch: the same problem, gate (STEP_TOL) and
+    guard as the linear test above, against _crafted_robust_step.  Curvature weight: the library's default
+    (ptzba.HUBER_CURVATURE = 0.1), so the floor branch of w2 is taken by a share of the records
+    (loss_ref.negative_curvature_share) and Huber's outer branch scales by it."""
+    import ptzba
+    p, weight, _, _ = _crafted(kind)
+    hc = ptzba.HUBER_CURVATURE
+    dx = _crafted_robust_step(kind, loss, hc, "disp")
+    dx_plain = _crafted_robust_step(kind, loss, hc, "plain")
+    tol = STEP_TOL[precision]
+    moved = _step_err(dx_plain, dx)
+    assert moved >= 10 * tol, moved
+    h = _handle(p, precision, loss=ptzba.LOSS_IDS[loss], records=(p.frame, p.landmark, p.xy, weight))
+    h.set_huber_curvature(hc)
+    info, merge = h.k1_info(), h.k1_merge_info()
+    assert 1 <= info[2] < info[1], info  # at least one workgroup on either frame-table path
+    assert merge["one_record"] == (kind == "one_record"), merge
+    dx_gpu, _ = _gpu_step(h, p)
+    h.close()
+    err = _step_err(dx_gpu, dx)
+    print(f"crafted {kind} {loss} precision {precision}: step error {err:.3e} (tol {tol:.0e}); displacement-free "
+          f"step {moved:.3e} away; k1_info {info}; {merge}")
+    assert err < tol, err
+
+
+@pytest.mark.parametrize("loss", ["linear", "huber", "soft_l1", "cauchy", "arctan"])
+@pytest.mark.parametrize("precision", [0, 1])
+def test_one_record_kernel_without_displacement_on_both_table_paths(gpu_available, precision, loss):
+    """k_linearize_one's displacement-free instantiations under every loss with workgroups on both table paths (the
+    merge tests run it on 140 frames, inside the LDS table): k1_cases' own observations in the one-record pair form, no
+    displacement set, against _crafted_robust_step without one; STEP_TOL and the library's default curvature weight as
+    above."""
+    import ptzba
+    p, weight, _, _ = _crafted("one_record_plain")
+    hc = ptzba.HUBER_CURVATURE
+    dx = _crafted_robust_step("one_record_plain", loss, hc, "plain")
+    tol = STEP_TOL[precision]
+    h = _handle(p, precision, loss=ptzba.LOSS_IDS[loss], lam=None, records=(p.frame, p.landmark, p.xy, weight))
+    h.set_huber_curvature(hc)
+    info, merge = h.k1_info(), h.k1_merge_info()
+    assert 1 <= info[2] < info[1], info
+    assert merge["one_record"] and h.displacement_info()[0] == 0, (merge, h.displacement_info())
+    dx_gpu, _ = _gpu_step(h, p)
+    h.close()
+    err = _step_err(dx_gpu, dx)
+    print(f"crafted one_record_plain {loss} precision {precision}: step error {err:.3e} (tol {tol:.0e}); k1_info {info}")
     assert err < tol, err
 
 
