@@ -500,7 +500,10 @@ PTZBA_EXPORT int ptzba_accept(ptzba_handle h, int accept);
  * the row b^T at n_aug and the padding diagonal; a build of the device-driven LM (ptzba_lm_build) on one GPU without
  * priors writes those itself (lambda D_pose on the pose diagonal, b^T in row n_aug, 1 on padding rows, 1e300 at
  * (n_aug, n_aug)) unless PTZBA_NO_FUSED_PREP is set or sys_ptr has been asked for before (a caller that holds the
- * pointer may sum the system between build and solve), which leave it raw as well. */
+ * pointer may sum the system between build and solve), which leave it raw as well.  This caller-exchange mode
+ * (switched on by asking for sys_ptr or scal_ptr here, or for the buffer of ptzba_exchange_packed) belongs to the
+ * handle, not to the problem: it outlives ptzba_set_problem, and priors, the displacement and the covariance calls
+ * stay refused on such a handle. */
 PTZBA_EXPORT int ptzba_exchange(ptzba_handle h, void** sys_ptr, int64_t* sys_count, void** scal_ptr);
 /* Packed exchange for sharded solves: a contiguous device buffer (fp64, *count doubles) holding only
  * the tiles of the reduced system the Schur kernel can write, then b | g_pose | dU.  Sequence per

@@ -634,6 +634,9 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   for (double& d : h->disp) d = 0.0;
   h->w_override = nullptr;
   h->trial_open = false;
+  // ... and without the pending decision of a device-driven run that stopped between ptzba_lm_solve and ptzba_lm_decide
+  // (the between-solves calls would refuse the new problem for it)
+  h->scal_deferred = false;
   h->ptz_saved.release();
   h->rays_saved.release();
   h->n_pose = n_pose;
@@ -825,6 +828,8 @@ int ptzba_problem_info(ptzba_handle h, int64_t* info) {
                                     &h->rays_trial, &h->D_pose, &h->D_ray, &h->ft, &h->rt, &h->ug_slot[0],
                                     &h->ug_slot[1], &h->w_slot[0], &h->w_slot[1], &h->lm_out[0], &h->lm_out[1], &h->lm_aux, &h->lm_red, &h->sys,
                                     &h->scal});
+  // the host fronts upload the permutation on first use: until then the buffer is the previous problem's
+  if (!h->perm_uploaded) info[7] -= (int64_t)h->perm.bytes;
   return 0;
 }
 

@@ -22,11 +22,11 @@ import numpy as np
 import pytest
 
 import k1_cases as kc
+from reuse_cases import N_POSE, pair_form as craft, segments as _segments  # noqa: F401  (shared with the reuse tests)
 from test_k1_merge_cpu import numpy_runs
 
 pytestmark = pytest.mark.gpu
 
-N_POSE = 140  # > K1_SEGW frames: the every-frame landmarks of k1_cases are walked in two windows
 LOSSES = {"linear": ("linear", 1.0, 1.0), "huber": ("huber", 1.0, 1.0), "huber_c0.1_s2.5": ("huber", 0.1, 2.5)}
 # merged against unmerged (and the one-record form against the general kernel) in fp64, relative: 10 x the worst
 # measured over this file's cases, floor 1e-13.  Measured: cost 1.7e-16, trial cost 2.6e-15, the step scalars 2.3e-14,
@@ -46,55 +46,6 @@ def _knob_off(name="PTZBA_K1_MERGE"):
             del os.environ[name]
         else:
             os.environ[name] = old
-
-
-def _segments(frame, landmark):
-    """Sorted order, each sorted record's position in its segment and its segment's first sorted record."""
-    n = len(frame)
-    o = np.lexsort((np.arange(n), frame, landmark))
-    key = landmark[o].astype(np.int64) * N_POSE * 4 + frame[o]
-    start = np.concatenate([[True], key[1:] != key[:-1]])
-    first = np.maximum.accumulate(np.where(start, np.arange(n), 0))
-    size = np.diff(np.flatnonzero(np.concatenate([start, [True]])))[np.cumsum(start) - 1]  # records of its segment
-    return o, np.arange(n) - first, first, start, size
-
-
-def craft(shape, extra=0):
-    """A k1_cases problem (N_POSE frames, ~2,400 records) put into pair form: see the module docstring for the shapes."""
-    k = (shape, extra)
-    if k in _cache:
-        return _cache[k]
-    u, v, ptz0, rays0, frame, landmark, xy, _ = kc.craft(n_pose=N_POSE, extra=extra)
-    o, pos, first, start, size = _segments(frame, landmark)
-    rng = np.random.default_rng(11)
-    xs = xy[o]
-    one = xs[first]  # every record of a segment at the segment's first keypoint
-    weight = None
-    if shape in ("one_run", "w_const", "w_split", "below_half", "above_half"):
-        xs = one.copy()
-    elif shape == "aaba":  # segments of four records and more: the third keeps its own observation, A A B A A ...
-        xs = np.where(((pos == 2) & (size >= 4))[:, None], xs, one)
-    else:
-        raise ValueError(shape)
-    if shape == "w_const":  # one user weight per segment: the runs stay, their weights are multiplicity x weight
-        weight = np.empty(len(frame))
-        weight[o] = rng.choice([1.0, 2.0, 3.0, 5.0], len(frame))[first]
-    if shape == "w_split":  # weights that differ inside a segment (of four records and more) split its runs
-        weight = np.empty(len(frame))
-        weight[o] = np.where(((pos == 2) | (pos == 3)) & (size >= 4), 2.0, 1.0)
-    if shape in ("below_half", "above_half"):
-        # runs = floor(R / 2) (merged) or one more (not merged): the last record of as many multi-record segments as
-        # that takes moves by an eighth of a pixel
-        n, runs = len(frame), int(start.sum())
-        want = n // 2 + (1 if shape == "above_half" else 0)
-        last = np.flatnonzero(np.concatenate([start[1:], [True]]) & (pos >= 1))
-        assert want - runs <= len(last), (n, runs, len(last))
-        xs = xs.copy()
-        xs[last[:want - runs], 0] += 0.125
-    out = xy.copy()
-    out[o] = xs
-    _cache[k] = (u, v, ptz0, rays0, frame, landmark, out, weight)
-    return _cache[k]
 
 
 def _lin(shape, extra, loss_id):
