@@ -1192,9 +1192,11 @@ void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hi
   const int n_free = a.n_pose - n_fixed;
   if (n_free <= 0) return;
   // fp32: the matrix cores (fp16 hi/lo splits; pipe 1 / 2: the producer / consumer form with waves 0-3 / the even
-  // waves staging, 0: k_schur_mf); fp64: the VALU kernel
+  // waves staging, 0: k_schur_mf; 3: the VALU kernel on the float32 slots -- float32 products, fp64 flush per batch --
+  // for the covariance build, whose error the split-fp16 products would dominate); fp64: the VALU kernel
   if (n_items > 0) {
-    if (sizeof(real) == 4 && pipe == 1) hipLaunchKernelGGL(k_schur_mfp<false>, dim3(n_items), dim3(512), 0, st, a);
+    if (sizeof(real) == 4 && pipe == 3) hipLaunchKernelGGL(k_schur<real>, dim3(n_items), dim3(512), 0, st, a);
+    else if (sizeof(real) == 4 && pipe == 1) hipLaunchKernelGGL(k_schur_mfp<false>, dim3(n_items), dim3(512), 0, st, a);
     else if (sizeof(real) == 4 && pipe == 2) hipLaunchKernelGGL(k_schur_mfp<true>, dim3(n_items), dim3(512), 0, st, a);
     else if (sizeof(real) == 4) hipLaunchKernelGGL(k_schur_mf, dim3(n_items), dim3(512), 0, st, a);
     else hipLaunchKernelGGL(k_schur<real>, dim3(n_items), dim3(512), 0, st, a);
