@@ -172,7 +172,7 @@ PTZBA_EXPORT int ptzba_k1_info(ptzba_handle h, int64_t* info4);
  * more than half the records, so the runs cannot halve them), [1] 1 when the kernel reads the
  * merged stream, [2] 1 when that stream holds exactly one record per segment and the kernel without a record phase
  * runs (PTZBA_K1_ONE=0: the general kernel), [3] 0.  Both knobs are read by every ptzba_set_problem call (as
- * PTZBA_K2_PIPE is), not once per handle.  ptzba_problem_info's n_obs stays the caller's record count. */
+ * PTZBA_K2_PROLOGUE is), not once per handle.  ptzba_problem_info's n_obs stays the caller's record count. */
 PTZBA_EXPORT int ptzba_k1_merge_info(ptzba_handle h, int64_t* out4);
 /* the reduced-system kernel's work items (each runs its landmark list in batches of 16, two batches per round of
  * its operand ring): [0] items, [1] chunk-0 items (they also sum the diagonal terms), [2] / [3] shortest / longest
@@ -186,7 +186,7 @@ PTZBA_EXPORT int ptzba_k2_info(ptzba_handle h, int* info8);
 PTZBA_EXPORT int ptzba_k2_tile_info(ptzba_handle h, int32_t* out8);
 /* host only (ptzba_version 0.7): which launch path the handle's reduced-system builds took since ptzba_set_problem:
  * [0] builds enqueued with the prologue launch in front (zeroing + landmark damping: the host-step API, fp64,
- * PTZBA_K2_PIPE=0, pose / marginal priors, PTZBA_NO_FUSED_PREP, covariance, ranks), [1] builds whose prologue is
+ * pose / marginal priors, PTZBA_NO_FUSED_PREP, covariance, ranks), [1] builds whose prologue is
  * folded into the reduced-system kernel and the trial kernel (device-driven single-GPU fp32 solves), [2] 1 when
  * PTZBA_K2_PROLOGUE=1 forces the prologue launch for every build, [3] zero */
 PTZBA_EXPORT int ptzba_build_info(ptzba_handle h, int64_t* out4);

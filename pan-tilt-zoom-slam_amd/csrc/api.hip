@@ -696,9 +696,6 @@ int ptzba_set_problem(ptzba_handle h, int32_t n_pose, int32_t n_landmark, int64_
   std::copy(L.k2_info, L.k2_info + 8, h->k2_info);
   std::copy(L.k2_tile_info, L.k2_tile_info + 8, h->k2_tile_info);
   h->f1_covered = L.f1_covered;
-  // PTZBA_K2_PIPE=0: the block-synchronous k_schur_mf (kept for one round: A/B and the bitwise parity test);
-  // =even: the even waves stage instead of waves 0-3
-  h->k2_pipe = getenv_is("PTZBA_K2_PIPE", "0") ? 0 : (getenv_is("PTZBA_K2_PIPE", "even") ? 2 : 1);
   // PTZBA_K2_PROLOGUE=1: keep the k_build_prologue launch in front of every build (build_impl)
   h->k2_prologue = getenv_is("PTZBA_K2_PROLOGUE", "1");
   h->n_build_prologue = h->n_build_folded = 0;
@@ -1179,10 +1176,10 @@ int ptzba::build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   // system raw for callers that sum it between build and solve (include/ptzba.h, the round-2 protocol)
   if (sel && h->fused_prep())
     fp = FusedPrep{h->row_pad.as<uint8_t>(), h->n_aug, h->info.as<int>(), h->D_pose.as<double>(), lambda, lam_dev};
-  // Device-driven single-GPU fp32 builds on the producer / consumer K2 need no prologue launch: K2 zeroes the
+  // Device-driven single-GPU fp32 builds on the matrix-core K2 need no prologue launch: K2 zeroes the
   // pattern tiles, the vectors and info itself and forms the landmark damping in its list build, k_trial forms its
   // own and keeps D_ray (SchurArgs::ztiles, lm_damp).  Every other build launches the prologue as before.
-  const bool fold = sel && fp.pad && h->precision == PTZBA_FP32 && h->k2_pipe != 0 && !h->k2_prologue &&
+  const bool fold = sel && fp.pad && h->precision == PTZBA_FP32 && !h->k2_valu32 && !h->k2_prologue &&
                     h->n_s2_items > 0 && h->n_pose - h->n_fixed > 0;
   if (!fold)
     launch_build_prologue(h->S(), h->ld, h->ztiles.as<int2>(), h->n_ztiles, h->bvec(), 3 * h->ld,
@@ -1221,9 +1218,9 @@ int ptzba::build_impl(ptzba_ctx* h, double lambda, const double* lam_dev, const 
   a.D_ray = h->D_ray.as<double>();
   tm_begin(h, TM_SCHUR);
   if (h->precision == PTZBA_FP32)
-    launch_schur<float>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, h->k2_pipe);
+    launch_schur<float>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, h->k2_valu32);
   else
-    launch_schur<double>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, 0);
+    launch_schur<double>(a, h->n_s2_items, h->n_s2_groups, h->n_fixed, h->st, false);
   tm_end(h, TM_SCHUR);
   // pose priors: S += P, g_pose += P e, b -= P e, dU += diag P at the build's state (not part of the timed Schur group)
   // (with_priors == false: ptzba_marginal_prior's build of the dropped records alone)

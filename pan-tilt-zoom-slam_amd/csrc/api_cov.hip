@@ -114,23 +114,23 @@ static int cov_dof(const ptzba_ctx* h, const char* who, const ptzba_cov_opts& op
 }
 
 // the caller's run state a covariance call borrows: huber curvature, damping, timing groups, and the fp32 K2 form.
-// The one build of a covariance call runs the VALU K2 (launch_schur's form 3: float32 products of the float32 slots,
+// The one build of a covariance call runs the VALU K2 (k2_valu32: float32 products of the float32 slots,
 // flushed to fp64 per batch): the matrix-core K2's split-fp16 products (22 bits, rounded toward zero) leave an error
 // in S that an LM step tolerates but an inverse multiplies by the condition number -- 3.5e-3 in the block metric at
 // scaled cond 1.6e5 against ~5e-5 from the float32 slots themselves (crafted systems).
-constexpr int K2_FORM_VALU = 3;
 struct CovBorrow {
   ptzba_ctx* h;
   double hcurv, lambda;
-  int timing, k2_pipe;
+  int timing;
+  bool k2_valu32;
   explicit CovBorrow(ptzba_ctx* h_)
-      : h(h_), hcurv(h_->hcurv), lambda(h_->lambda), timing(h_->timing), k2_pipe(h_->k2_pipe) {
+      : h(h_), hcurv(h_->hcurv), lambda(h_->lambda), timing(h_->timing), k2_valu32(h_->k2_valu32) {
     h->hcurv = 1.0;
     h->lambda = 0.0;
     h->timing = 0;
-    h->k2_pipe = K2_FORM_VALU;
+    h->k2_valu32 = true;
   }
-  ~CovBorrow() { h->hcurv = hcurv; h->lambda = lambda; h->timing = timing; h->k2_pipe = k2_pipe; }
+  ~CovBorrow() { h->hcurv = hcurv; h->lambda = lambda; h->timing = timing; h->k2_valu32 = k2_valu32; }
 };
 
 // queues, under a CovBorrow: the start event, the linearisation with IRLS curvature, the residual sum of scale mode 2

@@ -54,8 +54,8 @@ struct ptzba_ctx {
   DBuf s2_items, s2_groups, s2_lm, lm_meta;  // K2 work items / tiles / lists, slot ranges
   DBuf s2_part, part_diag;                                    // K2 split partials (blocks, diagonal terms)
   int n_s2_items = 0, n_s2_groups = 0;
-  int k2_pipe = 1;     // fp32 K2 kernel: 1 producer / consumer waves (waves 0-3 stage), 2 (even waves stage), 0 k_schur_mf
-                       // (3, the VALU k_schur<float>, only for the length of a covariance call: api_cov.hip CovBorrow)
+  bool k2_valu32 = false;  // fp32 build on the VALU kernel k_schur<float> instead of the matrix-core k_schur_mfp, for
+                           // the length of a covariance call (api_cov.hip CovBorrow)
   int k2_info[8] = {};  // ptzba_k2_info
   bool k2_prologue = false;  // PTZBA_K2_PROLOGUE=1: every build launches k_build_prologue (A/B, tests)
   int64_t n_build_prologue = 0, n_build_folded = 0;  // builds enqueued on either path (ptzba_build_info)

@@ -292,7 +292,7 @@ const char* layout_k2(ProblemLayout& L, int n_pose, int n_lm, int n_fixed) {
   int64_t total_w = 0;
   for (size_t k = 0; k < tiles.size(); ++k)
     total_w += (int64_t)tiles[k].size() * (tile_key[2 * k + 1] == 0 ? W0 : WD);
-  // item target: at most 256 (ONE round of one 512-thread workgroup per CU: k_schur_mf's ~100 KB of LDS allows one
+  // item target: at most 256 (ONE round of one 512-thread workgroup per CU: k_schur_mfp's 116 KB of LDS allows one
   // per CU) -- same-box A/B at config 3 (r04j, r04p): 256 items 64.7-64.8 us per build against 73.3-74.6 with 512
   // (two rounds), 68.0 with 192, 84.8 with 320; proportionally fewer for less work -- a rank's shard of a sharded
   // solve: each item's 74 KB split partial and the reduce over its tile's splits are fixed costs (measured at

@@ -296,7 +296,7 @@ void launch_linearize(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0
 template <typename real>
 void launch_linearize_one(const LinArgs& a, int loss, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 template <typename real>
-void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, int pipe);
+void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, bool valu32);
 // scratch: RED_SCRATCH doubles (partials + counter), zero-initialised once, reused across calls
 constexpr int RED_SCRATCH = 64 * 8 + 2;
 // scal[8] | loc[8] | info -> one packed device block (read back with a single copy)

@@ -325,29 +325,49 @@ __global__ __launch_bounds__(512) void k_schur(SchurArgs a) {
 #endif
 }
 // ------------------------------------------------------------------------------------------------
-// K2 on the matrix cores (fp32 path, the default): the same work items, split partials and diagonal
-// terms as k_schur; each batch of 16 landmarks is one k-step (K = 16 landmarks x 2 ray dimensions) of
-// v_mfma_f32_16x16x32_f16 over the item's 96 x 192 block S(F1 dofs, chunk dofs) -- 72 output blocks of
-// 16 x 16, nine per wave (3 row blocks x 3 column blocks).  Zero products (a landmark covers ~19 % of a
-// tile) cost matrix-core cycles instead of VALU issue.
+// K2 on the matrix cores (k_schur_mfp: the fp32 path): the same work items, split partials and diagonal terms as
+// k_schur; each batch of 16 landmarks is one k-step (K = 16 landmarks x 2 ray dimensions) of
+// v_mfma_f32_16x16x32_f16 over the item's 96 x 192 block S(F1 dofs, chunk dofs) -- 72 output blocks of 16 x 16.
+// Zero products (a landmark covers ~19 % of a tile) cost matrix-core cycles instead of VALU issue.
 // Precision: every operand is split x = hi + lo into two fp16 (22 significant bits) and a product is
 // hi*hi + hi*lo + lo*hi (the dropped lo*lo is ~2^-22 of it), accumulated in fp32 over the item's batches
-// and stored as the fp32 split partial (the reduce sums the splits in fp64).  Range: W (~1e4 px^2) and Y = -W V~^-1 (~1) would not both fit fp16, so row
-// k = (landmark, d) of W is scaled by g_l = 2^round(log2 sqrt(tr V~_l^-1)) and the same row of Y by
-// 1 / g_l: the product Y^T W is unchanged (powers of two: exact), both factors ~ sqrt(|W| |Y|).
+// and stored as the fp32 split partial (the reduce sums the splits in fp64).
+// Range: W (~1e4 px^2) and Y = -W V~^-1 (~1) would not both fit fp16, so row k = (landmark, d) of W is scaled by
+// g_l = 2^round(log2 sqrt(tr V~_l^-1)) and the same row of Y by 1 / g_l: the product Y^T W is unchanged (powers of
+// two: exact), both factors ~ sqrt(|W| |Y|).
 // The focal-length rows of both operands are ~2^8 below the pan / tilt rows (d x / d f = (x - u) / f ~ 0.1 against
 // d x / d pan ~ f pi / 180 ~ 50 px / deg), so their lo halves fell below fp16's normal range (6e-5) and kept only a few
 // bits -- at lambda = 0 the undamped step of tests/test_gpu_k1_paths.py was off by up to 8.6e-3 of its largest entry,
 // reproduced to three digits by a CPU emulation of this split.  Those rows are staged times MF_FROW = 2^7 (still below
 // the pan / tilt rows: no new overflow) and the accumulators of the f rows / columns scaled back: exact.
+// Roles: the eight waves take fixed roles, so that the staging of one batch (loads, g_l scaling, fp16 splits, LDS
+// writes: VALU + memory issue) runs beside the products of another (fragment reads + MFMAs) on every SIMD:
+//   * waves 0-3 stage: per batch each thread loads four W slots of the chunk's frames and two (landmark, f1) pairs,
+//     scales and splits them and writes the operand rows; V~^-1, g_l and V~^-1 g come from a per-landmark LDS table
+//     built with the list.  On chunk-0 items the thread that stages Y of a pair also sums that pair's diagonal terms
+//     (U, g_pose, W V~^-1 g; HBM-bound, ~100 MB per build), their loads issued with the pair's, under the MFMAs;
+//   * waves 4-7 multiply: 18 output blocks each (3 row blocks x 6 column blocks), per block al*bh, ah*bl, ah*bh in
+//     batch order, then the partial store.
+// Hand-off: a ring of NR operand buffers and two LDS counter sets, one counter per wave and one writer per counter:
+// s_ready[w] = b + 1 once staging wave w's part of batch b is in LDS (after lgkmcnt(0)), s_done[w] = b + 1 once
+// product wave w holds batch b's fragments in registers (after lgkmcnt(0)).  A product wave starts batch b when all
+// four s_ready >= b + 1; a staging wave re-fills the buffer of batch b - NR when all four s_done >= b - NR + 1.
+// Why it cannot stall: the counters live in LDS and are zeroed before the one __syncthreads that precedes
+// every wait; the skip_if exit is taken by whole workgroups before it; the batch count nb is block-uniform,
+// so all eight waves run the same number of hand-offs; a counter only grows, and the wait of batch b on
+// either side needs only signals of batches < b from the other side (s_ready of b needs s_done of
+// b - NR, which needs s_ready of b - NR): the dependency chain ends at batch 0, which waits for
+// nothing.  No wait looks at global memory or at another workgroup.
+// Folded build prologue (SchurArgs::ztiles != nullptr: device-driven single-GPU builds, api.hip build_impl): the
+// launch also does k_build_prologue's work, so that launch is not needed.  The list build forms V~^-1, g_l and
+// V~^-1 g from K1's landmark row, D_ray and lambda (lm_damp: the prologue's fp64 expressions; it only reads), and the
+// product waves, idle until the first batch is staged, zero the pattern tiles of S, b | g_pose | dU and info[0].
+// A launch that leaves at skip_if zeroes nothing: the next solve's first build zeroes for itself.
+// ------------------------------------------------------------------------------------------------
 constexpr float MF_FROW = 128.f;
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 typedef float f4v __attribute__((ext_vector_type(4)));
-constexpr int MKP = 40;
-#ifndef MF_DIAG_FUSED
-#define MF_DIAG_FUSED 1  // chunk-0 diagonal terms inside the batch pipeline (0: a phase before it)
-#endif
-// (k pitch of an operand row in halves: 80-B rows keep the 16-B fragment reads aligned)
+constexpr int MKP = 40;  // k pitch of an operand row in halves: 80-B rows keep the 16-B fragment reads aligned
 
 // (x0, x1) -> hi + lo, each a packed pair of fp16 (v_cvt_pkrtz: toward zero; x - hi is exact in fp32 and
 // has at most 13 significant bits, of which lo keeps 11)
@@ -357,300 +377,6 @@ __device__ __forceinline__ void split_pk(float x0, float x1, hp2v& h, hp2v& l) {
   l = __builtin_amdgcn_cvt_pkrtz(x0 - (float)h[0], x1 - (float)h[1]);
 }
 
-template <typename real, bool AGENT>
-__device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4 g, int e);
-template <bool AGENT>
-__device__ __forceinline__ void schur_reduce_vec(const SchurArgs& a, const int4 g, int tid);
-
-__global__ __launch_bounds__(512) void k_schur_mf(SchurArgs a) {
-  constexpr int SNB = 16;                // landmarks per batch
-  constexpr int NSL = SNB * WAVE / 512;  // W slots staged per thread per batch
-  __shared__ __attribute__((aligned(16))) _Float16 sY[2][2][3 * SF][MKP];     // [buf][hi|lo][q*32 + f1][2j + d]
-  __shared__ __attribute__((aligned(16))) _Float16 sWt[2][2][3 * WAVE][MKP];  // [buf][hi|lo][r*64 + f2][2j + d]
-  __shared__ int4 sL[SCHUR_LMAX];
-  __shared__ float sG[SCHUR_LMAX];  // g_l per landmark of the list
-  if (a.skip_if && *a.skip_if) return;
-#ifdef SK_TIMING
-  const bool skrec = threadIdx.x == 0 && blockIdx.x < 16;
-  long long* sk = g_sk[blockIdx.x & 15];
-  if (skrec)
-    for (int k = 0; k < 16; ++k) sk[k] = 0;
-#endif
-  long long skt = 0;
-  (void)skt;
-  SK_T(0);
-  const int item = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int4 it = a.items[item];
-#ifdef SK_TIMING
-  if (threadIdx.x == 0 && item < 4096) {
-    g_sk_items[item][0] = __builtin_amdgcn_s_memrealtime();
-    g_sk_items[item][2] = it.y;
-    g_sk_items[item][3] = it.w - it.z;
-  }
-#endif
-  const int f1b = it.x, chunk = it.y, lb = it.z, nl = it.w - it.z;
-  const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;
-  const int f2base = f1b + WAVE * chunk;
-  const bool alt = a.sel && *a.sel;  // device-chosen linearisation slot
-  const float* __restrict__ w_slot = (const float*)(alt ? a.w_slot1 : a.w_slot);
-  for (int k = t; k < nl; k += 512) {
-    const int4 m = a.item_lm[lb + k];
-    sL[k] = m;
-    const double* vi = a.lm_aux + (int64_t)m.x * 8;
-    int e = 0;
-    (void)frexp(vi[0] + vi[2], &e);
-    sG[k] = ldexpf(1.f, e / 2);
-  }
-  __syncthreads();
-  SK_T(1);
-#if !MF_DIAG_FUSED
-  if (chunk == 0) schur_diag_terms<float>(a, sL, nl, f1b, item, alt, reinterpret_cast<double*>(&sWt[0][0][0][0]));
-#endif
-
-  // staging registers of one batch (two sets: the loads of batch p + 2 are issued while batch p is
-  // multiplied and batch p + 1 staged, so each load has two batches of MFMA time to arrive)
-  struct Pre {
-    float rw[NSL][6], rgw[NSL], ryw[6], ryg, rvi[3];
-    bool rwin[NSL], ryin;
-  };
-  const int yj = t / SF, yi = t & (SF - 1);
-  auto fetch = [&](Pre& P, int p) {  // landmarks [p, p + SNB) of the list (clamped, branch-free)
-#pragma unroll
-    for (int q = 0; q < NSL; ++q) {
-      const int e = t + 512 * q, j = e >> 6, ln = e & 63;
-      const int jj = min(p + j, nl - 1);
-      const int4 m = sL[jj];
-      const int idx = f2base + ln - m.y;
-      P.rwin[q] = (p + j < nl) && idx >= 0 && f2base + ln <= m.z;
-      P.rgw[q] = sG[jj];
-      slot_load6(P.rw[q], w_slot + (int64_t)(m.w + min(max(idx, 0), m.z - m.y)) * W_STRIDE);
-    }
-    const int f = f1b + yi, jj = min(p + yj, nl - 1);
-    const int4 m = sL[jj];
-    P.ryin = (p + yj < nl) && f >= m.y && f <= m.z;
-    P.ryg = sG[jj];
-    slot_load6(P.ryw, w_slot + (int64_t)(m.w + min(max(f - m.y, 0), m.z - m.y)) * W_STRIDE);
-    const double* vi = a.lm_aux + (int64_t)m.x * 8;
-    P.rvi[0] = (float)vi[0]; P.rvi[1] = (float)vi[1]; P.rvi[2] = (float)vi[2];
-  };
-  auto stage = [&](const Pre& P, int buf) {
-#pragma unroll
-    for (int q = 0; q < NSL; ++q) {
-      const int e = t + 512 * q, j = e >> 6, ln = e & 63;
-      const float gq = P.rwin[q] ? P.rgw[q] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        hp2v h, l;
-        const float gr = r == 2 ? gq * MF_FROW : gq;
-        split_pk(P.rw[q][2 * r] * gr, P.rw[q][2 * r + 1] * gr, h, l);
-        *reinterpret_cast<hp2v*>(&sWt[buf][0][r * WAVE + ln][2 * j]) = h;
-        *reinterpret_cast<hp2v*>(&sWt[buf][1][r * WAVE + ln][2 * j]) = l;
-      }
-    }
-    // Y / g = -(W / g) V~^-1, staged negated: the products accumulate -Y W^T (fp32 is exact enough: the
-    // operand keeps 22 bits).  1 / g is a power of two: exact.
-    const float gi = P.ryin ? 1.f / P.ryg : 0.f;
-    const float v0 = P.rvi[0] * gi, v1 = P.rvi[1] * gi, v2 = P.rvi[2] * gi;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const float W0 = P.ryw[2 * q], W1 = P.ryw[2 * q + 1];
-      hp2v h, l;
-      const float sq = q == 2 ? -MF_FROW : -1.f;
-      split_pk(sq * fmaf(W0, v0, W1 * v1), sq * fmaf(W0, v1, W1 * v2), h, l);
-      *reinterpret_cast<hp2v*>(&sY[buf][0][q * SF + yi][2 * yj]) = h;
-      *reinterpret_cast<hp2v*>(&sY[buf][1][q * SF + yi][2 * yj]) = l;
-    }
-  };
-
-  const int rg = wv >> 2, cg = wv & 3;             // row blocks 3rg.., column blocks 3cg..
-  const int fr = lane & 15, fk = (lane >> 4) * 8;  // fragment row / column and k offset of this lane
-  // the item's products accumulate in fp32 over all its batches (<= 32 of 16 landmarks); the split partial is
-  // stored in fp32 anyway, and round 6 measured fp64 flushes every 4 batches (72 more VGPRs: spills, and an early
-  // vmcnt(0) in the loop) as no more accurate: max |S32 - S64| / sqrt(S_ii S_jj) 2.87e-7 / 4.24e-7 at configs 2 / 3
-  // against 2.90e-7 / 3.93e-7, 3 us faster per build (profiles/r06_k2_ab.json)
-  f4v c[3][3];
-#pragma unroll
-  for (int x = 0; x < 3; ++x)
-#pragma unroll
-    for (int y = 0; y < 3; ++y) c[x][y] = f4v{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int buf) {
-    h8v bh[3], bl[3];
-#pragma unroll
-    for (int y = 0; y < 3; ++y) {
-      const int col = 16 * (3 * cg + y) + fr;
-      bh[y] = *reinterpret_cast<const h8v*>(&sWt[buf][0][col][fk]);
-      bl[y] = *reinterpret_cast<const h8v*>(&sWt[buf][1][col][fk]);
-    }
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const int row = 16 * (3 * rg + x) + fr;
-      const h8v ah = *reinterpret_cast<const h8v*>(&sY[buf][0][row][fk]);
-      const h8v al = *reinterpret_cast<const h8v*>(&sY[buf][1][row][fk]);
-#pragma unroll
-      for (int y = 0; y < 3; ++y) {
-        c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[y], c[x][y], 0, 0, 0);
-        c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[y], c[x][y], 0, 0, 0);
-        c[x][y] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[y], c[x][y], 0, 0, 0);
-      }
-    }
-  };
-  SK_T(2);
-#if MF_DIAG_FUSED
-  // chunk-0 items: the diagonal terms (U, g_pose, W V~^-1 g of the F1 frames; HBM-bound, ~100 MB per
-  // build) ride in the batch pipeline instead of a phase of their own: the thread that stages Y of
-  // (landmark, f1) also sums that pair's terms, its U|g loads issued one batch ahead, under the MFMAs.
-  const bool diag = chunk == 0;
-  const float* __restrict__ ug_slot = (const float*)(alt ? a.ug_slot1 : a.ug_slot);
-  float du[9];
-  double dvg[2];  // converted where they are consumed (daccum): a conversion here would wait for the load at once
-  float dacc[12];  // fp32 over the item's <= 32 batches: one term per batch (the reduction below is fp64)
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dacc[k] = 0.f;
-  auto dfetch = [&](int p) {
-    const int4 m = sL[min(p + yj, nl - 1)];
-    const int64_t slot = m.w + min(max(f1b + yi - m.y, 0), m.z - m.y);
-    slot_load9(du, ug_slot + slot * UG_STRIDE);
-    const double* vi = a.lm_aux + (int64_t)m.x * 8;
-    dvg[0] = vi[3];
-    dvg[1] = vi[4];
-  };
-  auto daccum = [&](const Pre& P) {
-    if (P.ryin) {
-      const float g0 = (float)dvg[0], g1 = (float)dvg[1];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) dacc[k] += du[k];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) dacc[9 + q] += fmaf(P.ryw[2 * q], g0, P.ryw[2 * q + 1] * g1);
-    }
-  };
-#else
-  constexpr bool diag = false;
-  auto dfetch = [&](int) {};
-  auto daccum = [&](const Pre&) {};
-#endif
-  Pre A, B;
-  if (nl > 0) {
-    if (diag) dfetch(0);
-    fetch(A, 0);
-    fetch(B, SNB);
-    stage(A, 0);
-    if (diag) daccum(A);
-  }
-  __syncthreads();
-  SK_T(3);
-#ifdef SK_TIMING
-  if (skrec) {
-    sk[8] = nl;
-    sk[9] = chunk;
-  }
-#endif
-  // batch p in buffer 0 from set A, batch p + SNB in buffer 1 from set B (block-uniform control flow)
-  for (int p = 0; p < nl; p += 2 * SNB) {
-    SK_NOW(skt);
-    if (diag && p + SNB < nl) dfetch(p + SNB);
-    fetch(A, p + 2 * SNB);
-    SK_ACC(11, skt);  // fetch issue (list reads, addresses, loads)
-    SK_NOW(skt);
-    compute(0);
-    SK_ACC(4, skt);
-    SK_NOW(skt);
-    if (p + SNB < nl) {
-      stage(B, 1);
-      if (diag) daccum(B);
-    }
-    SK_ACC(5, skt);
-    SK_NOW(skt);
-    __syncthreads();
-    SK_ACC(6, skt);
-    if (p + SNB >= nl) break;
-    SK_NOW(skt);
-    if (diag && p + 2 * SNB < nl) dfetch(p + 2 * SNB);
-    fetch(B, p + 3 * SNB);
-    SK_ACC(11, skt);
-    SK_NOW(skt);
-    compute(1);
-    SK_ACC(4, skt);
-    SK_NOW(skt);
-    if (p + 2 * SNB < nl) {
-      stage(A, 0);
-      if (diag) daccum(A);
-    }
-    SK_ACC(5, skt);
-    SK_NOW(skt);
-    __syncthreads();
-    SK_ACC(6, skt);
-  }
-  SK_T(7);
-#if MF_DIAG_FUSED
-  if (diag) {  // fixed-order reduction over the 16 landmark lanes of each frame (as schur_diag_terms)
-    double* red = reinterpret_cast<double*>(&sWt[0][0][0][0]);  // free after the last batch's barrier
-#pragma unroll
-    for (int k = 0; k < 12; ++k) red[(yj * SF + yi) * 12 + k] = (double)dacc[k];
-    __syncthreads();
-    if (t < SF * 12) {
-      double v = 0;
-      for (int j0 = 0; j0 < 512 / SF; ++j0) v += red[j0 * SF * 12 + t];
-      a.part_diag[(int64_t)item * SF * 12 + t] = v;
-    }
-  }
-#endif
-  // partial blocks of this split: part[item][f1 local][3q + r][f2], as k_schur writes them
-  float* out = (float*)a.part + (int64_t)item * (SF * 9 * WAVE);
-#pragma unroll
-  for (int x = 0; x < 3; ++x)
-#pragma unroll
-    for (int y = 0; y < 3; ++y)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int row = 16 * (3 * rg + x) + (lane >> 4) * 4 + v, col = 16 * (3 * cg + y) + fr;
-        const int q = row / SF, i = row % SF, r = col / WAVE, f2 = col % WAVE;
-        const float back = (q == 2 ? 1.f / MF_FROW : 1.f) * (r == 2 ? 1.f / MF_FROW : 1.f);  // (exact: powers of two)
-        out[(i * 9 + 3 * q + r) * WAVE + f2] = c[x][y][v] * back;
-      }
-  SK_T(10);
-#ifdef SK_TIMING
-  __syncthreads();
-  if (threadIdx.x == 0 && item < 4096) g_sk_items[item][1] = __builtin_amdgcn_s_memrealtime();
-#endif
-}
-
-// ------------------------------------------------------------------------------------------------
-// Producer / consumer form of k_schur_mf (the fp32 default; PTZBA_K2_PIPE=0 keeps k_schur_mf): the same
-// work items, operand layout, arithmetic and partials, but the eight waves take fixed roles so that the
-// staging of one batch (loads, g_l scaling, fp16 splits, LDS writes: VALU + memory issue) runs beside the
-// products of another (fragment reads + MFMAs) on every SIMD instead of before them:
-//   * 4 staging waves: what fetch / stage / dfetch / daccum of k_schur_mf do, each thread with twice the
-//     elements (four W slots, two (landmark, f1) pairs -- the same element -> LDS location map, and one
-//     dacc set per pair as before, so every sum keeps its order; which thread takes which element is
-//     free, see MF_WMAP); V~^-1, g_l and V~^-1 g come from a per-landmark LDS table built with the list;
-//   * 4 product waves: 18 output blocks each (3 row blocks x 6 column blocks), per block al*bh, ah*bl,
-//     ah*bh in batch order as before, then the partial store.
-// Hand-off: a ring of MF_RING operand buffers and two LDS counter sets, one counter per wave and one
-// writer per counter: s_ready[w] = b + 1 once staging wave w's part of batch b is in LDS (after
-// lgkmcnt(0)), s_done[w] = b + 1 once product wave w holds batch b's fragments in registers (after
-// lgkmcnt(0)).  A product wave starts batch b when all four s_ready >= b + 1; a staging wave re-fills the
-// buffer of batch b - MF_RING when all four s_done >= b - MF_RING + 1.
-// Why it cannot stall: the counters live in LDS and are zeroed before the one __syncthreads that precedes
-// every wait; the skip_if exit is taken by whole workgroups before it; the batch count nb is block-uniform,
-// so all eight waves run the same number of hand-offs; a counter only grows, and the wait of batch b on
-// either side needs only signals of batches < b from the other side (s_ready of b needs s_done of
-// b - MF_RING, which needs s_ready of b - MF_RING): the dependency chain ends at batch 0, which waits for
-// nothing.  No wait looks at global memory or at another workgroup.
-// Folded build prologue (SchurArgs::ztiles != nullptr: device-driven single-GPU builds, api.hip build_impl): the
-// launch also does k_build_prologue's work, so that launch is not needed.  The list build forms V~^-1, g_l and
-// V~^-1 g from K1's landmark row, D_ray and lambda (lm_damp: the prologue's fp64 expressions; it only reads), and the
-// product waves, idle until the first batch is staged, zero the pattern tiles of S, b | g_pose | dU and info[0].
-// A launch that leaves at skip_if zeroes nothing: the next solve's first build zeroes for itself.
-// ------------------------------------------------------------------------------------------------
-#ifndef MF_RING
-#define MF_RING 2  // operand buffers in the ring (2: 116 KB of LDS; 3: 159 KB, measured no faster)
-#endif
-#ifndef MF_STAGGER
-#define MF_STAGGER 0
-#endif
-#ifndef MF_WMAP
-#define MF_WMAP 1
-#endif
 __device__ __forceinline__ void k2_signal(int* p, int v) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores / fragment reads are done
   if (lane_id() == 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -670,11 +396,9 @@ __device__ __forceinline__ void k2_wait4(const int* p, int v) {
   asm volatile("" ::: "memory");
 }
 
-// EVEN: the even waves stage (else waves 0-3)
-template <bool EVEN>
 __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
   constexpr int SNB = 16;                // landmarks per batch
-  constexpr int NR = MF_RING;
+  constexpr int NR = 2;                  // operand buffers in the ring: 116 KB of LDS (a ring of 3, 159 KB, measured no faster)
   constexpr int NSL = SNB * WAVE / 256;  // W slots staged per staging thread per batch
   constexpr int NYP = SNB * SF / 256;    // (landmark, f1) pairs per staging thread per batch
   __shared__ __attribute__((aligned(16))) _Float16 sY[NR][2][3 * SF][MKP];     // [buf][hi|lo][q*32 + f1][2j + d]
@@ -687,8 +411,8 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
   static_assert(sizeof(sWt) >= 512 * 12 * sizeof(double), "the diagonal terms' reduction reuses sWt");
   if (a.skip_if && *a.skip_if) return;
   const int t = threadIdx.x, lane = lane_id(), wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const bool prod = EVEN ? !(wv & 1) : wv < 4;
-  const int rk = EVEN ? wv >> 1 : wv & 3;  // rank inside the role
+  const bool prod = wv < 4;  // producer of operands: waves 0-3 stage, waves 4-7 multiply
+  const int rk = wv & 3;     // rank inside the role
 #ifdef SK_TIMING
   const bool skrec = lane == 0 && rk == 0 && blockIdx.x < 16;  // first staging and first product wave
   long long* sk = g_sk[blockIdx.x & 15];
@@ -763,21 +487,13 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
     };
     // element map of a staging thread: W slot q -> (landmark j of the batch, frame ln of the chunk), pair u ->
     // (landmark yj, frame yi of F1).  Any bijection gives the same LDS contents and the same sums (one dacc set per
-    // pair).  MF_WMAP 0: k_schur_mf's order (a wave = 64 consecutive frames of one landmark; its b32 LDS stores hit
-    // rows 80 B apart: 16 banks, 4-way conflicts); 1: a wave = 16 consecutive frames x 4 landmarks, whose stores
-    // (bank = 20 frame + landmark mod 64) reach all 64 banks; a landmark's loads still run over 16 consecutive slots
-    // (384 B).
-#if MF_WMAP
+    // pair).  A wave takes 16 consecutive frames x 4 landmarks: its b32 LDS stores (rows 80 B apart: bank = 20 frame +
+    // landmark mod 64) reach all 64 banks, where 64 consecutive frames of one landmark hit 16 banks four ways; a
+    // landmark's loads still run over 16 consecutive slots (384 B).
     auto wj = [&](int) { return (lane >> 4) + 4 * rk; };
     auto wln = [&](int q) { return (lane & 15) + 16 * q; };
     auto pyj = [&](int) { return (lane >> 4) + 4 * rk; };
     auto pyi = [&](int u) { return (lane & 15) + 16 * u; };
-#else
-    auto wj = [&](int q) { return (pt + 256 * q) >> 6; };
-    auto wln = [&](int q) { return (pt + 256 * q) & 63; };
-    auto pyj = [&](int u) { return pt / SF + (256 / SF) * u; };
-    auto pyi = [&](int) { return pt & (SF - 1); };
-#endif
     auto fetch = [&](Pre& P, int p) {  // landmarks [p, p + SNB) of the list (clamped, branch-free)
 #pragma unroll
       for (int q = 0; q < NSL; ++q) {
@@ -819,7 +535,8 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
           *reinterpret_cast<hp2v*>(&sWt[buf][1][r * WAVE + ln][2 * j]) = l;
         }
       }
-      // Y / g = -(W / g) V~^-1, staged negated (as k_schur_mf)
+      // Y / g = -(W / g) V~^-1, staged negated: the products accumulate -Y W^T (fp32 is exact enough: the operand
+      // keeps 22 bits).  1 / g is a power of two: exact.
 #pragma unroll
       for (int u = 0; u < NYP; ++u) {
         const int yj = pyj(u), yi = pyi(u);
@@ -836,7 +553,7 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
         }
       }
     };
-    float dacc[NYP][12];  // fp32 over the item's <= 32 batches, one set per pair (as k_schur_mf)
+    float dacc[NYP][12];  // fp32 over the item's <= 32 batches, one term per batch and pair (the reduction below is fp64)
 #pragma unroll
     for (int u = 0; u < NYP; ++u)
 #pragma unroll
@@ -853,11 +570,6 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
         }
     };
     Pre A, B;
-#if MF_STAGGER
-    // the four staging waves start MF_STAGGER * 64 cycles apart, so that their load bursts do not meet in the CU's
-    // one address path (they do the same work per batch and keep the offset)
-    for (int k = 0; k < rk; ++k) __builtin_amdgcn_s_sleep(MF_STAGGER);
-#endif
     if (nb > 0) {
       fetch(A, 0);
       // (keeps set A's loads ahead of set B's in issue order, as in the loop: interleaved here, the loop's first
@@ -905,7 +617,7 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
       sk[11] = tk2;
     }
 #endif
-    if (diag) {  // fixed-order reduction over the 16 landmark lanes of each frame (as k_schur_mf)
+    if (diag) {  // fixed-order reduction over the 16 landmark lanes of each frame (as schur_diag_terms)
       k2_wait4(s_done, nb);  // the last fragment reads of the ring have landed: sWt is free
       double* red = reinterpret_cast<double*>(&sWt[0][0][0][0]);
 #pragma unroll
@@ -954,7 +666,11 @@ __global__ __launch_bounds__(512) void k_schur_mfp(SchurArgs a) {
         if (a.prep.pad && pt == 0) a.prep.info[0] = 0;
       }
     }
-    f4v c[3][6];  // fp32 over all the item's batches (see k_schur_mf)
+    // the item's products accumulate in fp32 over all its batches (<= 32 of 16 landmarks); the split partial is
+    // stored in fp32 anyway, and round 6 measured fp64 flushes every 4 batches (72 more VGPRs: spills, and an early
+    // vmcnt(0) in the loop) as no more accurate: max |S32 - S64| / sqrt(S_ii S_jj) 2.87e-7 / 4.24e-7 at configs 2 / 3
+    // against 2.90e-7 / 3.93e-7, 3 us faster per build (profiles/r06_k2_ab.json)
+    f4v c[3][6];
 #pragma unroll
     for (int x = 0; x < 3; ++x)
 #pragma unroll
@@ -1026,22 +742,16 @@ extern "C" int ptzba_debug_sk_items(long long* out) {
 }
 #endif
 
-// split-partial loads of the tile reduction (AGENT: agent-scope loads; the reduce launch uses plain ones).  Round 3-4
-// also reduced each tile in its LAST split (k_schur_mf "folded reduce", counters per tile): 258 us per build with an
-// acq_rel counter, not faster with write-through partials; removed in round 5 with the chunk-pair k_schur_mf2 (103 vs
-// 70 us per build, r03ab).
-template <typename real, bool AGENT>
-__device__ __forceinline__ real part_load(const real* p) {
-  if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else return *p;
-}
+// The tile reduction is a launch of its own and reads the split partials with plain loads.  (Rounds 3-4 also reduced
+// each tile in its last split, with agent-scope loads and a counter per tile: 258 us per build with an acq_rel
+// counter, not faster with write-through partials; removed in round 5.)
 // lane `lane`'s copy of v (wave-uniform lane index; reads the register whether or not that lane is still active)
 __device__ __forceinline__ double lane_read(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
 }
-template <typename real, bool AGENT>
+template <typename real>
 __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4 g, int e) {
   constexpr int NE = SF * 9 * WAVE;
   const int f1b = g.x, chunk = g.y;
@@ -1061,7 +771,7 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
   const double* pd = a.part_diag + (int64_t)i * 12 + ui;
   const bool tile0 = chunk == 0 && f1 < a.n_pose;  // (wave-uniform)
   double uc = 0;
-  if (tile0) uc = part_load<double, AGENT>(pd + (int64_t)min(g.z + ln, last) * (SF * 12));
+  if (tile0) uc = pd[(int64_t)min(g.z + ln, last) * (SF * 12)];
   // (the fused prepare's damping operands of the diagonal lane: with the same round trip)
   const bool damp = a.prep.pad && q == r && f2 == f1;
   double Dv = 0, lambda = 0;
@@ -1079,12 +789,12 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
     real x[8], y[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      x[u] = part_load<real, AGENT>(p + (int64_t)min(g.z + u, last) * NE + (unsigned)e);
+      x[u] = p[(int64_t)min(g.z + u, last) * NE + (unsigned)e];
       y[u] = 0;
     }
     if (g.z + 8 < g.w) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) y[u] = part_load<real, AGENT>(p + (int64_t)min(g.z + 8 + u, last) * NE + (unsigned)e);
+      for (int u = 0; u < 8; ++u) y[u] = p[(int64_t)min(g.z + 8 + u, last) * NE + (unsigned)e];
     }
     for (int it = g.z;;) {
 #pragma unroll
@@ -1097,7 +807,7 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
       if (it + 8 < g.w) {
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          y[u] = part_load<real, AGENT>(p + (int64_t)min(it + 8 + u, last) * NE + (unsigned)e);
+          y[u] = p[(int64_t)min(it + 8 + u, last) * NE + (unsigned)e];
       }
     }
   }
@@ -1114,7 +824,7 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
     }
     if (diag)
       for (int it2 = g.z + WAVE; it2 < g.w; ++it2) {  // (a tile of more than 64 splits: the rest one by one)
-        const double uu = part_load<double, AGENT>(pd + (int64_t)it2 * (SF * 12));
+        const double uu = pd[(int64_t)it2 * (SF * 12)];
         v += uu;
         du += uu;
       }
@@ -1132,7 +842,6 @@ __device__ __forceinline__ void schur_reduce_elem(const SchurArgs& a, const int4
   if (pf2 >= col0) a.S[(pf2 + r) * ld + col0 + q] = v;
   else a.S[(col0 + q) * ld + pf2 + r] = v;
 }
-template <bool AGENT>
 __device__ __forceinline__ void schur_reduce_vec(const SchurArgs& a, const int4 g, int tid) {
   const int f1b = g.x;
   // threads [0, 3 SF): g_pose and sum W V~^-1 g of (frame, q2) -> b, g_pose; threads [3 SF, 6 SF): diag U -> dU.
@@ -1152,8 +861,8 @@ __device__ __forceinline__ void schur_reduce_vec(const SchurArgs& a, const int4 
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const double* ps = pd + (int64_t)min(it2 + u, last) * (SF * 12);
-      x0[u] = part_load<double, AGENT>(ps);
-      x1[u] = part_load<double, AGENT>(diag ? ps : ps + 3);
+      x0[u] = *ps;
+      x1[u] = *(diag ? ps : ps + 3);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u)
@@ -1183,22 +892,19 @@ template <typename real>
 __global__ __launch_bounds__(256, sizeof(real) == 4 ? 8 : 6) void k_schur_reduce(SchurArgs a) {
   if (a.skip_if && *a.skip_if) return;
   const int4 g = a.groups[blockIdx.y];  // {f1b, chunk, first item, end item}
-  schur_reduce_elem<real, false>(a, g, blockIdx.x * 256 + threadIdx.x);
-  if (g.y == 0 && blockIdx.x == 0 && threadIdx.x < SF * 6) schur_reduce_vec<false>(a, g, threadIdx.x);
+  schur_reduce_elem<real>(a, g, blockIdx.x * 256 + threadIdx.x);
+  if (g.y == 0 && blockIdx.x == 0 && threadIdx.x < SF * 6) schur_reduce_vec(a, g, threadIdx.x);
 }
 
 template <typename real>
-void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, int pipe) {
+void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hipStream_t st, bool valu32) {
   const int n_free = a.n_pose - n_fixed;
   if (n_free <= 0) return;
-  // fp32: the matrix cores (fp16 hi/lo splits; pipe 1 / 2: the producer / consumer form with waves 0-3 / the even
-  // waves staging, 0: k_schur_mf; 3: the VALU kernel on the float32 slots -- float32 products, fp64 flush per batch --
-  // for the covariance build, whose error the split-fp16 products would dominate); fp64: the VALU kernel
+  // fp32: the matrix cores (fp16 hi/lo splits), or with valu32 the VALU kernel on the float32 slots -- float32
+  // products, fp64 flush per batch -- for the covariance build, whose error the split-fp16 products would dominate;
+  // fp64: the VALU kernel
   if (n_items > 0) {
-    if (sizeof(real) == 4 && pipe == 3) hipLaunchKernelGGL(k_schur<real>, dim3(n_items), dim3(512), 0, st, a);
-    else if (sizeof(real) == 4 && pipe == 1) hipLaunchKernelGGL(k_schur_mfp<false>, dim3(n_items), dim3(512), 0, st, a);
-    else if (sizeof(real) == 4 && pipe == 2) hipLaunchKernelGGL(k_schur_mfp<true>, dim3(n_items), dim3(512), 0, st, a);
-    else if (sizeof(real) == 4) hipLaunchKernelGGL(k_schur_mf, dim3(n_items), dim3(512), 0, st, a);
+    if (sizeof(real) == 4 && !valu32) hipLaunchKernelGGL(k_schur_mfp, dim3(n_items), dim3(512), 0, st, a);
     else hipLaunchKernelGGL(k_schur<real>, dim3(n_items), dim3(512), 0, st, a);
   }
   if (n_groups > 0)
@@ -1206,7 +912,7 @@ void launch_schur(const SchurArgs& a, int n_items, int n_groups, int n_fixed, hi
                        dim3(256), 0, st, a);
 }
 
-template void launch_schur<float>(const SchurArgs&, int, int, int, hipStream_t, int);
-template void launch_schur<double>(const SchurArgs&, int, int, int, hipStream_t, int);
+template void launch_schur<float>(const SchurArgs&, int, int, int, hipStream_t, bool);
+template void launch_schur<double>(const SchurArgs&, int, int, int, hipStream_t, bool);
 
 }  // namespace ptzba

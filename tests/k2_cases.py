@@ -18,6 +18,9 @@ Free frames start at 1, so the F1 blocks of 32 frames begin at 1, 33, 65, ...
             SCHUR_LMAX = 512 landmarks (32 batches; the cap binds instead of the split weight)
   e_*       operand ranges on the crafted structure at 96 poses: f in {800, 3000, 20000}, a 700-record segment beside
             single records, gross outliers of 300 and 1000 px (Huber weights down to 1e-3)
+  grid      synthetic.make_grid_problem: 120 poses, 5,324 landmarks, 1.29M records; lists of 151-206 landmarks (10-13
+            batches: more than k_schur_mfp's operand ring holds, so every item re-fills its buffers)
+  config2   synthetic.make_problem("config2"): lists of at most 43 landmarks (1-3 batches)
 """
 import numpy as np
 
@@ -27,7 +30,7 @@ from oracle import ptz_oracle as orc
 
 def tiny():
     """12 landmarks over 100 poses (3 seen by every frame, 9 by 12 consecutive frames): every K2 list has at most 16
-    landmarks, and the all-frame landmarks reach partner chunk 1.  (A dict, the form tests/test_gpu_k2_pipeline.py uses.)"""
+    landmarks, and the all-frame landmarks reach partner chunk 1.  (A dict; as_tuple gives the k1_cases form.)"""
     rng = np.random.default_rng(11)
     n_pose, u, v = 100, 640.0, 360.0
     frames = [np.arange(n_pose)] * 3 + [np.arange(s, s + 12) for s in range(0, 99, 11)][:9]
@@ -48,6 +51,15 @@ def tiny():
 
 def as_tuple(d):
     return d["u"], d["v"], d["ptz"], d["rays"], d["frame"], d["landmark"], d["xy"], None
+
+
+def synthetic_case(name):
+    """The generator's problems as they come (nothing moved away from the Huber unit: the tests run them with f_scale 1
+    and curvature 1, where the weights are continuous at the unit)."""
+    import synthetic
+    p = (synthetic.make_grid_problem(120, 6000, -20.0, 20.0, (-10.0, 0.0, 10.0), seed=3) if name == "grid"
+         else synthetic.make_problem(name, seed=0))
+    return p.u, p.v, p.init_ptz, p.init_rays, p.frame, p.landmark, p.xy, None
 
 
 def _away_from_huber_unit(u, v, ptz0, rays0, frame, landmark, xy):
@@ -173,6 +185,7 @@ E_VARIANTS = {
 }
 
 NAMES = ("crafted", "crafted_w", "tiny", "a", "b34", "b65", "b161", "b161gap", "c") + tuple(E_VARIANTS)
+PIPELINE_NAMES = ("tiny", "crafted", "grid", "config2")  # together: every shape of k_schur_mfp's hand-off
 _cache = {}
 
 
@@ -183,6 +196,8 @@ def problem(name):
             p = kc.craft(weighted=name == "crafted_w")
         elif name == "tiny":
             p = as_tuple(tiny())
+        elif name in ("grid", "config2"):
+            p = synthetic_case(name)
         elif name == "a":
             p = case_a()
         elif name == "b161gap":

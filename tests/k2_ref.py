@@ -148,7 +148,7 @@ def fp32_gates(model_metrics):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the arithmetic of k_schur_mf / k_schur_mfp
+# the arithmetic of k_schur_mfp
 # ---------------------------------------------------------------------------------------------------------------------
 def rtz16(x):
     """float32 -> float16 rounded toward zero (v_cvt_pkrtz_f16_f32): nearest-even, then one step towards zero where the
@@ -218,7 +218,8 @@ def plan_summary(tiles, n_pose):
                 tiles_past_n_pose=sum(t["f1b"] + WAVE * (t["chunk"] + 1) > n_pose for t in tiles))
 
 
-MUTATIONS = ("no_lo_hi", "drop_last_of_16k1", "drop_split9", "no_frow_backscale", "mirror_untransposed", "chunk0_only")
+MUTATIONS = ("no_lo_hi", "drop_last_of_16k1", "drop_split9", "no_frow_backscale", "mirror_untransposed", "chunk0_only",
+             "skip_batch", "stale_batch")
 
 
 def model_mf(problem, lam, loss="linear", hcurv=1.0, f_scale=1.0, ptz=None, rays=None, D_prev=None, win=None,
@@ -231,7 +232,9 @@ def model_mf(problem, lam, loss="linear", hcurv=1.0, f_scale=1.0, ptz=None, rays
     the item's batches; back-scaled, stored float32, the tile's splits summed in fp64.  Diagonal terms: float32 sums
     per (list position mod 16, frame) over the item's batches, then fp64.
     mutate: one of MUTATIONS (a deliberately wrong kernel: tests/test_k2_ref.py shows that the gates notice);
-    mirror_untransposed needs pos (system positions).  Also returns max_hi (largest |hi|), sub_lo (share of non-zero
+    mirror_untransposed needs pos (system positions); skip_batch and stale_batch are hand-off faults of the operand
+    ring in one work item of more than three batches: its third batch is never accumulated, or its products are
+    formed from the first batch's operands (a buffer consumed before its re-fill).  Also returns max_hi (largest |hi|), sub_lo (share of non-zero
     operands whose lo is subnormal in fp16) and the tile plan."""
     u, v, _, _, frame, landmark, xy, weight = problem
     ptz, rays = _point(problem, ptz, rays)
@@ -337,8 +340,12 @@ def model_mf(problem, lam, loss="linear", hcurv=1.0, f_scale=1.0, ptz=None, rays
             Ah, Al, Gh, Gl = mat(Yh, SF), mat(Yl, SF), mat(Bh, WAVE), mat(Bl, WAVE)
             acc = np.zeros((3 * SF, 3 * WAVE), f32)
             dacc = np.zeros((SNB, SF, 12), f32)
+            ring_fault = mutate in ("skip_batch", "stale_batch") and nl > 3 * SNB and not did[mutate]
             for p in range(0, nl, SNB):
                 k0, k1 = 2 * p, 2 * min(p + SNB, nl)
+                if ring_fault and p == 2 * SNB:  # (the products only: the diagonal terms do not pass through the ring)
+                    did[mutate] = True
+                    k0, k1 = (0, 0) if mutate == "skip_batch" else (0, 2 * SNB)
                 if mutate != "no_lo_hi":
                     acc = (acc + (Al[k0:k1].T @ Gh[k0:k1]).astype(f32)).astype(f32)
                 else:

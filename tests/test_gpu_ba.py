@@ -524,7 +524,7 @@ def test_save_restore_state_restarts_identically(gpu_available):
 
 @pytest.mark.parametrize("config,loss", [("config2", "linear"), ("config3", "huber")])
 def test_reduced_system_matrix_core_k2_matches_fp64(gpu_available, config, loss):
-    """K2 of the fp32 path runs on the matrix cores (k_schur_mf: fp16 hi/lo operand splits with power-of-
+    """K2 of the fp32 path runs on the matrix cores (k_schur_mfp: fp16 hi/lo operand splits with power-of-
     two landmark scaling); the fp64 path keeps the VALU kernel.  At the same linearisation point the two reduced camera systems (S | b | g_pose
     | diag U, the exchange region) agree to the fp32 record precision, element by element against each row's
     scale.  Both builds share the tile lists, landmark windows, splits, frame positions and the tile reduction, so an

@@ -64,7 +64,7 @@ def _one_item():
 
 def _open(p, loss, setting, monkeypatch, env=(), win=None):
     import ptzba
-    for name in ("PTZBA_K2_PIPE", "PTZBA_NO_FUSED_PREP", "PTZBA_K2_PROLOGUE"):
+    for name in ("PTZBA_NO_FUSED_PREP", "PTZBA_K2_PROLOGUE"):
         monkeypatch.delenv(name, raising=False)
     if setting is not None:
         monkeypatch.setenv("PTZBA_K2_PROLOGUE", setting)

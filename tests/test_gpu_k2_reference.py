@@ -1,4 +1,4 @@
-"""K2's reduced camera system S | b | g_pose | diag U (k_schur<double>, k_schur_mf, k_schur_mfp, k_schur_reduce and the
+"""K2's reduced camera system S | b | g_pose | diag U (k_schur<double>, k_schur_mfp, k_schur_reduce and the
 tile / list / split builder of ptzba_set_problem) pinned entry by entry to the dense fp64 reference of tests/k2_ref.py on
 the problems of tests/k2_cases.py.  The reference knows no tiles, lists, splits or windows, so what the fp32 and fp64
 kernels share is not common-mode here.
@@ -19,8 +19,12 @@ import k2_ref as kr
 pytestmark = pytest.mark.gpu
 
 LOSSES = {"linear": ("linear", 1.0, 1.0), "huber_c0.1_s2.5": ("huber", 0.1, 2.5)}
+# the pipeline shapes' losses: the curvature weight 1 is continuous at the Huber unit, so an fp32 branch flip among the
+# grid problem's million records cannot move the reference
+PIPELINE_LOSSES = {"linear": LOSSES["linear"], "huber_c1_s1": ("huber", 1.0, 1.0)}
+LOSS_SETTINGS = dict(LOSSES, **PIPELINE_LOSSES)
 FP64, FP32 = 0, 1
-KERNELS = {"fp64": (FP64, None), "fp32": (FP32, None), "fp32_pipe0": (FP32, "0"), "fp32_even": (FP32, "even")}
+KERNELS = {"fp64": FP64, "fp32": FP32}  # k_schur<double> | k_schur_mfp, each with its k_schur_reduce
 _cache = {}
 
 
@@ -46,7 +50,7 @@ def _struct(name, ordering=None):
 
 def _ref(name, lam, loss_id, state=None, D_prev=None, tag=None):
     """The reference at the case's x0 (or at `state`, cached under `tag`): computed once, never modified."""
-    loss, hcurv, f_scale = LOSSES[loss_id]
+    loss, hcurv, f_scale = LOSS_SETTINGS[loss_id]
     ptz, rays = state if state is not None else (None, None)
     return _memo(("ref", name, lam, loss_id, tag),
                  lambda: kr.reduced_system(k2c.problem(name), lam, loss, hcurv, f_scale, ptz, rays, D_prev))
@@ -54,7 +58,7 @@ def _ref(name, lam, loss_id, state=None, D_prev=None, tag=None):
 
 def _model(name, lam, loss_id, state=None, D_prev=None, tag=None):
     """The arithmetic model's result and its own metrics against the reference."""
-    loss, hcurv, f_scale = LOSSES[loss_id]
+    loss, hcurv, f_scale = LOSS_SETTINGS[loss_id]
     ptz, rays = state if state is not None else (None, None)
 
     def make():
@@ -68,13 +72,9 @@ def _model(name, lam, loss_id, state=None, D_prev=None, tag=None):
 def _open(name, kernel, loss_id, monkeypatch, ordering=None):
     """set_problem + the shape assertions + set_state + curvature + linearize."""
     import ptzba
-    precision, pipe = KERNELS[kernel]
-    if pipe is None:
-        monkeypatch.delenv("PTZBA_K2_PIPE", raising=False)
-    else:
-        monkeypatch.setenv("PTZBA_K2_PIPE", pipe)
+    precision = KERNELS[kernel]
     u, v, ptz0, rays0, frame, landmark, xy, weight = k2c.problem(name)
-    loss, hcurv, f_scale = LOSSES[loss_id]
+    loss, hcurv, f_scale = LOSS_SETTINGS[loss_id]
     h = ptzba.BAHandle(0)
     h.set_problem(len(ptz0), len(rays0), frame, landmark, xy, u, v, weight=weight, precision=precision,
                   loss=ptzba.LOSS_HUBER if loss == "huber" else ptzba.LOSS_LINEAR, f_scale=f_scale,
@@ -106,7 +106,7 @@ def _check(what, name, kernel, loss_id, lam, view, rs, model=None, tight=True, f
     want = kr.expected_view(rs, lam, fused)
     ref = dict(rs, S=want["S"])
     e = kr.metrics(view, ref, view["mask"])
-    fp64 = KERNELS[kernel][0] == FP64
+    fp64 = KERNELS[kernel] == FP64
     gates = dict.fromkeys(e, kr.FP64_GATE) if fp64 else kr.fp32_gates(model["metrics"])
     line = f"K2REF {what} case={name} kernel={kernel} loss={loss_id} lam={lam:g} " + \
         " ".join(f"e_{k}={e[k]:.3e}" for k in ("S", "b", "g", "dU"))
@@ -133,7 +133,7 @@ def _run(name, kernel, loss_id, lams, monkeypatch, what="build", tight=True, ord
     for lam in lams:  # several builds on one linearisation: nothing of an earlier one survives in the written part
         h.build_reduced(lam)
         view = _view(h, name, ordering)
-        model = None if KERNELS[kernel][0] == FP64 else _model(name, lam, loss_id)
+        model = None if KERNELS[kernel] == FP64 else _model(name, lam, loss_id)
         out.append((view, _check(what, name, kernel, loss_id, lam, view, _ref(name, lam, loss_id), model, tight)))
     h.close()
     return out
@@ -148,7 +148,7 @@ def test_crafted_full_matrix(gpu_available, name, loss_id, kernel, monkeypatch):
     _run(name, kernel, loss_id, (0.0, 1e-2), monkeypatch)
 
 
-@pytest.mark.parametrize("kernel", ["fp64", "fp32", "fp32_pipe0"])
+@pytest.mark.parametrize("kernel", ["fp64", "fp32"])
 @pytest.mark.parametrize("name", ["tiny", "a", "b34", "b65", "b161", "b161gap"])
 def test_structure_cases(gpu_available, name, kernel, monkeypatch):
     """One-batch lists, split tiles (ten splits: the reduce's eight-in-flight loop and its remainder; three: the
@@ -247,7 +247,7 @@ def test_second_point_and_damping_memory(gpu_available, kernel, monkeypatch):
     rs = _ref(name, lam, loss_id, state, D1, tag)
     model = None if kernel == "fp64" else _model(name, lam, loss_id, state, D1, tag)
     e = _check("second_point", name, kernel, loss_id, lam, view, rs, model)
-    loss, hcurv, f_scale = LOSSES[loss_id]
+    loss, hcurv, f_scale = LOSS_SETTINGS[loss_id]
     rs_forgot = kr.reduced_system(p, lam, loss, hcurv, f_scale, state[0], state[1])
     forgot = kr.metrics(rs_forgot, rs, view["mask"])
     gate = kr.FP64_GATE if kernel == "fp64" else kr.fp32_gates(model["metrics"])["S"]
@@ -255,3 +255,75 @@ def test_second_point_and_damping_memory(gpu_available, kernel, monkeypatch):
     n3 = len(rs["b"])
     assert (rs["D"][n3:] > rs_forgot["D"][n3:]).any()  # some ray's scale is the remembered one
     assert forgot["S"] > gate >= e["S"]
+
+
+@pytest.mark.parametrize("kernel", list(KERNELS))
+@pytest.mark.parametrize("loss_id", list(PIPELINE_LOSSES))
+@pytest.mark.parametrize("name", k2c.PIPELINE_NAMES)
+def test_pipeline_shapes(gpu_available, name, loss_id, kernel, monkeypatch):
+    """The four problems that together run every shape of k_schur_mfp's hand-off (see
+    test_problems_cover_the_pipeline_shapes), lambda 0 and 1e-3 built one after the other.  The model's own error on
+    them is e_S <= 3.8e-7 and <= 2.3e-7 in the other metrics, so every fp32 gate is 10 x 1e-6 = 1e-5 (measured on
+    MI355X: fp32 e_S <= 2.1e-6, fp64 <= 2.3e-13 in every metric)."""
+    _run(name, kernel, loss_id, (0.0, 1e-3), monkeypatch, what="pipeline")
+
+
+def test_problems_cover_the_pipeline_shapes(gpu_available, monkeypatch):
+    """The four problems together run every shape of the hand-off: a single batch (nothing to re-fill), an odd batch
+    count beyond it (the batch staged after the two-batch loop), an even one, ragged last batches, and items with
+    and without the diagonal terms."""
+    infos = {}
+    for name in k2c.PIPELINE_NAMES:
+        h = _open(name, "fp32", "linear", monkeypatch)
+        infos[name] = h.k2_info()
+        h.close()
+        print(f"K2PIPE k2_info {name}: {infos[name]}")
+    for name, i in infos.items():
+        assert i["items"] >= 1 and 1 <= i["nl_min"] <= i["nl_max"] <= 512, (name, i)
+        assert i["nl_mod32_1_16"] + i["nl_mod32_17_31"] + i["nl_mod32_0"] == i["items"], (name, i)
+        assert 1 <= i["chunk0_items"] <= i["items"], (name, i)
+    t = infos["tiny"]
+    assert t["nl_max"] <= 16 and t["nl_le16"] == t["items"] and t["chunk0_items"] < t["items"], t
+    tot = {k: sum(i[k] for i in infos.values()) for k in infos["tiny"]}
+    assert tot["nl_le16"] > 0                            # one batch
+    assert tot["nl_mod32_1_16"] - tot["nl_le16"] > 0     # 3, 5, ... batches
+    assert tot["nl_mod32_17_31"] + tot["nl_mod32_0"] > 0  # an even batch count
+    assert tot["nl_mod32_17_31"] > 0                     # ... with a ragged last batch
+    assert any(i["nl_min"] % 16 for i in infos.values())
+    assert tot["chunk0_items"] > 0 and tot["items"] - tot["chunk0_items"] > 0
+    assert infos["grid"]["nl_min"] > 4 * 16              # more batches than ring buffers: every item re-fills them
+
+
+@pytest.mark.parametrize("kernel", ["fp64", "fp32"])
+def test_device_chosen_slot(gpu_available, kernel, monkeypatch):
+    """A build that reads the linearisation slot picked on the device (SchurArgs::sel): one device-driven LM trial from
+    lambda 1e-2, accepted by lm_decide, then the next trial's build.  Its region (fused layout) equals the reference
+    at the accepted state, at the damping the decision left, with the damping scales remembered from the first build
+    (as test_second_point_and_damping_memory shows for the host-step path).  fp32: both builds had the prologue folded
+    into K2, so the slot was read by k_schur_mfp's own list build as well.  Measured on MI355X: fp32 e_S 2.0e-6, e_g
+    6.3e-6 (gates 1e-5, 1.3e-5); fp64 e_g 9.5e-11 of the 1e-10 gate -- after the accepted step the gradient is a small
+    difference of large terms, and g_pose carries that cancellation in kernel and reference alike."""
+    import ptzba
+    name, loss_id, lam0 = "crafted", "linear", 1e-2
+    D1 = _ref(name, lam0, loss_id)["D"]
+    h = _open(name, kernel, loss_id, monkeypatch)
+    h.lm_start()
+    h.lm_init(ptzba.ptzba_lm_opts(1e-14, 1e-16, 0.0, lam0, 1e-12, 1e16, 3, 30, 0, 1.0, 0.0))
+    h.lm_build()
+    h.lm_solve()
+    h.lm_decide(0)
+    h.lm_build()
+    rec = h.lm_wait(0)
+    assert rec.accepted == 1 and rec.done == 0, (rec.accepted, rec.done, rec.status)
+    lam = float(rec.lam)
+    state = h.get_state()
+    assert not np.array_equal(state[0], k2c.problem(name)[2])
+    info = h.build_info()
+    view = _view(h, name)
+    h.close()
+    if kernel == "fp32":
+        assert info["folded_builds"] == 2 and info["prologue_builds"] == 0, info
+    tag = ("device_slot", kernel)  # the accepted state differs between the precisions
+    rs = _ref(name, lam, loss_id, state, D1, tag)
+    model = None if kernel == "fp64" else _model(name, lam, loss_id, state, D1, tag)
+    _check("device_slot", name, kernel, loss_id, lam, view, rs, model, fused=True)

@@ -87,7 +87,6 @@ def _factors():
 
 def _open(precision, monkeypatch, priors=False):
     import ptzba
-    monkeypatch.delenv("PTZBA_K2_PIPE", raising=False)
     monkeypatch.delenv("PTZBA_NO_FUSED_PREP", raising=False)
     u, v, ptz0, rays0, frame, landmark, xy, weight = _problem()
     h = ptzba.BAHandle(0)

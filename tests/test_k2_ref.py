@@ -148,13 +148,18 @@ def test_operand_ranges_fit_fp16():
             assert 0 < m["max_hi"] < 65504, (name, lam, m["max_hi"])
 
 
-@pytest.mark.parametrize("name", ["crafted", "a"])
+RING_MUTATIONS = {"skip_batch", "stale_batch"}  # hand-off faults: they need a work item of more than three batches
+
+
+@pytest.mark.parametrize("name", ["crafted", "a", "grid"])
 def test_the_gates_bite(name):
     """Each deliberately wrong kernel (k2_ref.MUTATIONS) that the case's structure can show exceeds the fp32 gate of
-    tests/test_gpu_k2_reference.py in at least one metric; printed: by how much."""
+    tests/test_gpu_k2_reference.py in at least one metric; printed: by how much.  The grid problem (lists of 10-13
+    batches) is there for the two faults of the operand ring alone, at the settings of test_pipeline_shapes."""
     import ptzba
     p = k2c.problem(name)
-    lam, loss = 1e-2, ("huber", 0.1, 2.5)
+    grid = name == "grid"
+    lam, loss = (1e-3, ("huber", 1.0, 1.0)) if grid else (1e-2, ("huber", 0.1, 2.5))
     win = _win(name)
     pos = ptzba.plan_export(win, 1, ptzba.ORDER_NESTED_FORCE)[0]
     rs = kr.reduced_system(p, lam, *loss)
@@ -163,7 +168,7 @@ def test_the_gates_bite(name):
     gates = kr.fp32_gates(base)
     assert base["S"] <= 1e-4
     applied = set()
-    for mut in kr.MUTATIONS:
+    for mut in (sorted(RING_MUTATIONS) if grid else kr.MUTATIONS):
         m = kr.model_mf(p, lam, *loss, win=win, mutate=mut, pos=pos)
         if not m["applied"]:
             continue
@@ -173,6 +178,9 @@ def test_the_gates_bite(name):
         print(f"K2REF mutation {name} {mut}: " + " ".join(f"{k}={e[k]:.2e}({excess[k]:.1f}x gate)" for k in e))
         assert max(excess.values()) > 1.0, (mut, e, gates)
     plan = kr.plan_summary(_plan(name), len(p[2]))
+    if grid:
+        assert plan["nl_min"] > 3 * kr.SNB and applied == RING_MUTATIONS, (plan, applied)
+        return
     want = {"no_lo_hi", "drop_last_of_16k1", "no_frow_backscale"}
     if plan["tiles_ge9_splits"]:
         want.add("drop_split9")
@@ -182,7 +190,20 @@ def test_the_gates_bite(name):
     if (((f[None, :] > f[:, None]) & (f[None, :] <= win[1:, None])) & (pos[f][None, :] < pos[f][:, None])).any():
         want.add("mirror_untransposed")
     assert applied == want, (applied, want)
-    # together the two cases show every mutation: the crafted problem has the far chunks (its all-frame landmarks
-    # couple every frame to the last, so no order but the natural one exists for it: nothing is mirrored), (a) the
-    # nine-split tile and, dissected once under ORDER_NESTED_FORCE, mirrored blocks
-    assert want == set(kr.MUTATIONS) - ({"drop_split9", "mirror_untransposed"} if name == "crafted" else {"chunk0_only"})
+    # together the two cases show every mutation but the ring's: the crafted problem has the far chunks (its all-frame
+    # landmarks couple every frame to the last, so no order but the natural one exists for it: nothing is mirrored),
+    # (a) the nine-split tile and, dissected once under ORDER_NESTED_FORCE, mirrored blocks
+    assert want == set(kr.MUTATIONS) - RING_MUTATIONS - ({"drop_split9", "mirror_untransposed"} if name == "crafted"
+                                                         else {"chunk0_only"})
+
+
+def test_ring_faults_need_more_than_three_batches():
+    """skip_batch and stale_batch cannot apply to the crafted problem (shown above: they are not among its applied
+    mutations) or to config2, whose lists have at most 43 landmarks: only the grid problem guards the ring."""
+    for name in ("crafted", "config2"):
+        assert kr.plan_summary(_plan(name), len(k2c.problem(name)[2]))["nl_max"] <= 3 * kr.SNB
+    p = k2c.problem("config2")
+    for mut in sorted(RING_MUTATIONS):
+        assert not kr.model_mf(p, 1e-3, "huber", 1.0, 1.0, win=_win("config2"), mutate=mut)["applied"]
+
+

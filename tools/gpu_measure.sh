@@ -22,5 +22,5 @@ timeout -s KILL 60 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/${TAG}_cal_
 timeout -s KILL 60 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/${TAG}_cal_write -o run --output-format csv -- ./tools/pmc_calib.bin > $OUT/${TAG}_cal_write.log 2>&1 || { echo CALFAIL; exit 1; }
 python tools/pmc_calib_summary.py $OUT/${TAG}_cal_fetch $OUT/${TAG}_cal_write $OUT/${TAG}_pmc_calib.json
 # K2 (matrix-core Schur kernel) traffic from the same PMC passes
-python tools/pmc_traffic.py $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write "k_schur_mf" config3/pair/fp32/huber/k2 $OUT/${TAG}_k2_traffic.json 1024 131072 > /dev/null || { echo K2TRAFFICFAIL; exit 1; }
+python tools/pmc_traffic.py $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write "k_schur_mfp" config3/pair/fp32/huber/k2 $OUT/${TAG}_k2_traffic.json 1024 131072 > /dev/null || { echo K2TRAFFICFAIL; exit 1; }
 cat $OUT/${TAG}_k2_traffic.json

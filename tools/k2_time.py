@@ -1,4 +1,4 @@
-"""Time K2 (k_schur_mf + k_schur_reduce: the bench's "schur" group, HIP events around every launch) alone at config 3
+"""Time K2 (k_schur_mfp + k_schur_reduce: the bench's "schur" group, HIP events around every launch) alone at config 3
 (fp32 + Huber): n ptzba_build_reduced calls after one linearisation.  PTZBA_LIB selects a variant library."""
 import os
 import sys

@@ -1,4 +1,4 @@
-"""Per-work-item timeline of K2 (k_schur_mf) from a -DSK_TIMING build (PTZBA_LIB): s_memrealtime start / end (100 MHz)
+"""Per-work-item timeline of K2 (k_schur_mfp) from a -DSK_TIMING build (PTZBA_LIB): s_memrealtime start / end (100 MHz)
 of every item of one build, its chunk and landmark count -> makespan, item-duration spread, how many items are still
 running over time (load balance of the one-round item schedule)."""
 import ctypes

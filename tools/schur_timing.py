@@ -1,8 +1,7 @@
-"""Phase timing of K2 (k_schur) from a -DSK_TIMING build (PTZBA_LIB): clock64 stamps of thread 0 of the
-first 16 workgroups: [list load, diag phase, first stage, batches: fetch / compute / stage / barrier sums, tail].
-Producer / consumer kernel (the default): fetch, stage and "barrier" (the wait for a free ring buffer) are the first
-staging wave's, compute and cwait (the wait for a staged batch) the first product wave's; PTZBA_K2_PIPE=0 times
-k_schur_mf, whose phases are all thread 0's."""
+"""Phase timing of K2 from a -DSK_TIMING build (PTZBA_LIB): clock64 stamps in the first 16 workgroups: [list load,
+diag phase, first stage, batches: fetch / compute / stage / barrier sums, tail].  k_schur_mfp (fp32): fetch, stage and
+"barrier" (the wait for a free ring buffer) are the first staging wave's, compute and cwait (the wait for a staged
+batch) the first product wave's; k_schur (fp64): all phases are thread 0's."""
 import ctypes
 import os
 import sys
