@@ -249,7 +249,9 @@ typedef struct {
 } ptzba_lm_opts;
 /* termination status (scipy least_squares numbering where it has one): DAMPING = the trial was rejected at
  * every damping up to max_lambda, i.e. no cost decrease is resolvable any more (scipy's trf ends such a run
- * through its xtol test once the trust radius collapses); FAILED = max_retries rejections in a row */
+ * through its xtol test once the trust radius collapses); FAILED = max_retries rejections in a row.  After a
+ * rejection lambda > max_lambda is tested first: a rejection that reaches max_retries and also pushes lambda past
+ * max_lambda reports DAMPING, in every loop (the device decision, ptzba_solve, ptzba.LMSolver's host loop) */
 enum {
   PTZBA_STATUS_FAILED = -1,
   PTZBA_STATUS_MAX_ITER = 0,

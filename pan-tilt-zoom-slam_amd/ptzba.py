@@ -2107,7 +2107,9 @@ class LMSolver:
                     if lam > self.max_lambda:
                         break
             if not accepted:
-                status = STATUS_DAMPING if retries < self.max_retries else -1
+                # DAMPING first, as the device decides (include/ptzba.h): the rejection that reaches max_retries may
+                # also be the one that pushes lambda past max_lambda
+                status = STATUS_DAMPING if lam > self.max_lambda else -1
                 break
             it += 1
             njev += 1

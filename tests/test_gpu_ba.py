@@ -480,21 +480,29 @@ def test_device_loop_equals_host_loop(gpu_available, config, precision, loss):
 
 
 def test_device_loop_rejections_and_limits(gpu_available):
-    """A huge initial damping forces rejected trials (re-linearisation path) and max_iter stops early."""
+    """The host and the device loop agree where max_iter stops early (lambda0=1e-9), where a huge initial damping
+    (lambda0=1e6) forces many small accepted steps -- it rejects nothing -- and from a far Gauss-Newton start
+    (tests/lm_cases.far_start) whose overshooting steps are rejected seven times in a row: nfev > njev + 1 proves the
+    rejections (the current linearisation kept across rejected trials)."""
     import ptzba
     import synthetic
+    import lm_cases
     p = synthetic.make_problem("config1", seed=2)
-    for kw in (dict(lambda0=1e-9, max_iter=3), dict(lambda0=1e6, max_iter=25)):
+    q = lm_cases.problem()
+    for kw, pr, start in ((dict(lambda0=1e-9, max_iter=3), p, p.init_ptz), (dict(lambda0=1e6, max_iter=25), p, p.init_ptz),
+                          (dict(gauss_newton=True, max_iter=5), q, lm_cases.far_start())):
         res = []
         for device_loop in (False, True):
             h = ptzba.BAHandle(0)
-            h.set_problem(p.n_pose, p.n_landmark, p.frame, p.landmark, p.xy, p.u, p.v, precision=0)
-            h.set_state(p.init_ptz, p.init_rays)
+            h.set_problem(pr.n_pose, pr.n_landmark, pr.frame, pr.landmark, pr.xy, pr.u, pr.v, precision=0)
+            h.set_state(start, pr.init_rays)
             res.append((ptzba.LMSolver(h, ftol=1e-10, xtol=1e-14, device_loop=device_loop, **kw).run(), h.get_state()))
             h.close()
         (a, sa), (b, sb) = res
         assert (a.njev, a.nfev, a.status) == (b.njev, b.nfev, b.status), (a, b)
         np.testing.assert_allclose(sb[0], sa[0], rtol=0, atol=1e-10)
+        if pr is q:
+            assert a.nfev > a.njev + 1 and b.nfev > b.njev + 1, (a, b)
 
 
 def test_save_restore_state_restarts_identically(gpu_available):
