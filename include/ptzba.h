@@ -474,7 +474,9 @@ PTZBA_EXPORT int ptzba_ray_prior_info(ptzba_handle h, double* out4);
  * Jacobian's f column gains d(x, y)/dq (l3, l4, l5), d(x, y)/dq is formed at the displaced q, and the structure of the
  * solve is unchanged.  Every path that projects follows: ptzba_linearize / step / accept, ptzba_lm_*, ptzba_solve,
  * ptzba_solve_resident, ptzba_residual, ptzba_covariance and ptzba_covariance_joint (the residual scale included) and
- * ptzba_marginal_prior.  ptz_refine_poses, ptz_pose_ransac and the ray map stay displacement-free.
+ * ptzba_marginal_prior.  Relocalisation follows through entry points of its own (ptzba_version 0.10):
+ * ptz_refine_poses_disp, ptz_pose_ransac_disp and ptz_back_project_rays_exact; ptz_refine_poses and ptz_pose_ransac
+ * stay displacement-free.
  *
  * The six values are copied.  NULL or six zeros clears the displacement: the handle then launches the kernels it
  * launches without this call, bit for bit.  Valid after ptzba_set_problem, between solves; cleared by
@@ -600,6 +602,16 @@ PTZBA_EXPORT int ptz_project_rays(int device, int64_t n, double u, double v, dou
 PTZBA_EXPORT int ptz_back_project_rays(int device, int64_t n, double u, double v, double f, double pan,
                                        double tilt, const double* displacement6, const double* xy,
                                        double* rays_out);
+/* The exact inverse of ptz_project_rays (ptzba_version 0.10).  ptz_back_project_rays is the reference's
+ * back_project_to_ray: it subtracts d(f) from the z = 1 point, which inverts the projection only without a
+ * displacement.  Here, with n = ((x - u) / f, (y - v) / f, 1), R = R_x(tilt) R_y(pan) and d = d(f), the direction
+ * p = (p0, p1, 1) solves R p + d = t n:  t = (1 + (R^T d)_z) / (R^T n)_z,  p = t R^T n - R^T d,  theta = atan p0,
+ * phi = atan(-p1 / sqrt(p0^2 + 1)).  valid_out[i] (may be NULL) is 0 when (R^T n)_z <= 0, t <= 0 or the result is not
+ * finite: the pixel has no ray in the (theta, phi) chart and rays_out[i] is NaN.  displacement6 NULL = zeros; a
+ * non-finite value is refused. */
+PTZBA_EXPORT int ptz_back_project_rays_exact(int device, int64_t n, double u, double v, double f, double pan,
+                                             double tilt, const double* displacement6, const double* xy /*[n][2]*/,
+                                             double* rays_out /*[n][2]*/, uint8_t* valid_out /*[n]*/);
 /* PtzSlam.compute_h_jacobian: H [2n][3+2n] row-major, dense, as the reference */
 PTZBA_EXPORT int ptz_h_jacobian(int device, int64_t n, double u, double v, double f, double pan,
                                 double tilt, const double* displacement6, const double* rays, double* H_out);
@@ -623,6 +635,16 @@ PTZBA_EXPORT int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, 
                                   const int64_t* subset_offsets, const int32_t* subset_index,
                                   const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
                                   int32_t* status_out);
+/* ptz_refine_poses under the displaced camera of ptzba_set_displacement (ptzba_version 0.10): the residual is
+ * x = u + f q0 / q2, y = v + f q1 / |q2| with q = R p + d(f), d(f) = (l0 + l3 f, l1 + l4 f, l2 + l5 f), and the
+ * Jacobian's f column carries d(x, y)/dq (l3, l4, l5); the damping, the acceptance and the stop rules are those of
+ * ptz_refine_poses.  displacement6 NULL or six zeros: ptz_refine_poses' kernel, bit for bit.  A non-finite value is
+ * refused with a message and ptz_inout is left untouched. */
+PTZBA_EXPORT int ptz_refine_poses_disp(int device, int32_t n_hyp, double* ptz_inout, int64_t n_corr,
+                                       const double* rays, const double* points, double u, double v,
+                                       const int64_t* subset_offsets, const int32_t* subset_index,
+                                       const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
+                                       int32_t* status_out, const double* displacement6);
 
 /* ---------------- pose RANSAC without an initial pose (map-wide relocalisation) ----------------
  * Robust (pan, tilt, f) from n_corr >= 2 ray-pixel correspondences (rays [n_corr][2] in degrees, points
@@ -657,6 +679,21 @@ PTZBA_EXPORT int ptz_pose_ransac(int device, int64_t n_corr, const double* rays,
                                  double* ptz_hyp_out /*3, winner before refit*/, int32_t* best_sample_out,
                                  int32_t* hyp_inliers_out, uint8_t* mask_out /*n_corr*/, int32_t* n_inliers_out,
                                  double* cost_out, int32_t* status_out /*0 found, 1 not found*/);
+/* ptz_pose_ransac under the displaced camera (ptzba_version 0.10).  A pixel a = (x - u, y - v) at focal length f sees
+ * q = t nh, nh = (a0, a1, f), and r = q - d(f) = R p has |r|^2 = |p|^2 =: m, so t is the positive root of
+ * t^2 |nh|^2 - 2 t (nh . d) + |d|^2 - m = 0.  The rotation keeps r_i . r_j = p_i . p_j: one equation g(f) = 0, solved
+ * by six Newton steps in f (analytic dg/df, the same count for every sample) from each accepted root of
+ * ptz_pose_ransac's closed form.  A candidate whose f ends non-finite or <= 0, or whose square-root argument was
+ * negative at a step, is dropped and its slot stays empty; pan and tilt follow from r_i(f) by ptz_pose_ransac's
+ * formulas.  Draws, retry rule, slot numbering (root = the closed-form root the iteration started from) and tie rule
+ * are ptz_pose_ransac's; scoring and the final mask use the displaced projection, the refit is ptz_refine_poses_disp's
+ * LM.  displacement6 NULL or six zeros: ptz_pose_ransac, bit for bit.  A non-finite value is refused with a message
+ * and every output is left untouched. */
+PTZBA_EXPORT int ptz_pose_ransac_disp(int device, int64_t n_corr, const double* rays, const double* points, double u,
+                                      double v, const ptz_pose_ransac_opts* opts, double* ptz_out /*3*/,
+                                      double* ptz_hyp_out /*3*/, int32_t* best_sample_out, int32_t* hyp_inliers_out,
+                                      uint8_t* mask_out /*n_corr*/, int32_t* n_inliers_out, double* cost_out,
+                                      int32_t* status_out, const double* displacement6);
 
 /* ---------------- host bookkeeping (native) ---------------- */
 /* ---------------- feature front-end (image_process.py:178-234, 418-441) ----------------

@@ -100,10 +100,12 @@ const char* ptzba_last_error(void) { return g_err.c_str(); }
 // 0.8: ptzba_covariance_joint (ptzba_cov_opts as 0.3).
 // 0.9: PTZBA_LOSS_SOFT_L1 / _CAUCHY / _ARCTAN (no struct changes; huber_curvature / curvature_switch are read for
 // every robust loss); ptzba_set_displacement / ptzba_displacement_info (no struct changes).
+// 0.10: ptz_refine_poses_disp / ptz_pose_ransac_disp / ptz_back_project_rays_exact (new entry points, no struct changes).
 const char* ptzba_version(void) {
-  return "ptzba 0.9 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
+  return "ptzba 0.10 gfx950 (ptzba_lm_opts: 11 fields as 0.2; ptzba_covariance as 0.3; ptzba_set_pose_priors as 0.4; "
          "ptzba_marginal_prior as 0.5; ptzba_set_ray_priors as 0.6; ptzba_build_info as 0.7; ptzba_covariance_joint "
-         "as ptzba 0.8; losses soft_l1 / cauchy / arctan; ptzba_set_displacement)";
+         "as ptzba 0.8; losses soft_l1 / cauchy / arctan; ptzba_set_displacement as 0.9; ptz_refine_poses_disp, "
+         "ptz_pose_ransac_disp, ptz_back_project_rays_exact)";
 }
 
 ptzba_handle ptzba_new(int device) {

@@ -92,6 +92,26 @@ int ptz_back_project_rays(int device, int64_t n, double u, double v, double f, d
   return 0;
 }
 
+int ptz_back_project_rays_exact(int device, int64_t n, double u, double v, double f, double pan, double tilt,
+                                const double* d6, const double* xy, double* rays_out, uint8_t* valid_out) {
+  if (n < 0) return fail("n < 0");
+  if (n == 0) return 0;
+  if (!xy || !rays_out) return fail("null argument");
+  if (d6)
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(d6[k])) return fail("displacement: non-finite value at index %d", k);
+  HIPCHK(hipSetDevice(device));
+  Tmp t;
+  double *dxy = t.in(xy, 2 * n), *dr = t.out(2 * n);
+  DBuf dvalid;
+  NEED(dxy && dr && dvalid.alloc((size_t)n) == 0);
+  launch_back_project_exact(n, u, v, f, pan, tilt, d6, dxy, dr, dvalid.as<uint8_t>(), nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(rays_out, dr, 2 * n * 8, hipMemcpyDeviceToHost));
+  if (valid_out) HIPCHK(hipMemcpy(valid_out, dvalid.p, (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ptz_h_jacobian(int device, int64_t n, double u, double v, double f, double pan, double tilt, const double* d6,
                    const double* rays, double* H_out) {
   if (n < 0) return fail("n < 0");

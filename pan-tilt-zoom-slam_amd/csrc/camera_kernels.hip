@@ -4,6 +4,7 @@
 //   k_project_rays   PTZCamera.project_ray (ptz_camera.py:191-210): K (R p + d), SIGNED q2,
 //                    displacement d = w[0:3] + w[3:6] f (ptz_camera.py:106-115)
 //   k_back_project   PTZCamera.back_project_to_ray (ptz_camera.py:287-312)
+//   k_back_project_exact  the exact inverse of k_project_rays (camera_model.h back_project_exact) with a validity flag
 //   k_h_jacobian     PtzSlam.compute_h_jacobian (ptz_slam.py:73-138): the same central differences
 //                    (0.001 deg, 0.1 px) of project_ray, written into the dense [2n, 3+2n] H
 #include "ptzba_common.h"
@@ -60,6 +61,20 @@ __global__ void k_back_project(int64_t n, double u, double v, double f, double p
   rays[2 * i + 1] = b;
 }
 
+__global__ void k_back_project_exact(int64_t n, double u, double v, double f, double pan, double tilt, Disp D, int has_d,
+                                     const double* __restrict__ xy, double* __restrict__ rays,
+                                     uint8_t* __restrict__ valid) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double R[3][3];
+  rot_tp(pan, tilt, R);
+  double a, b;
+  const bool ok = back_project_exact(u, v, f, R, D, has_d, xy[2 * i], xy[2 * i + 1], a, b);
+  rays[2 * i] = a;
+  rays[2 * i + 1] = b;
+  if (valid) valid[i] = ok ? 1 : 0;
+}
+
 __global__ void k_h_jacobian(int64_t n, double u, double v, double f, double pan, double tilt, Disp D, int has_d,
                              const double* __restrict__ rays, double* __restrict__ H) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,6 +117,13 @@ void launch_back_project(int64_t n, double u, double v, double f, double pan, do
   int has;
   Disp D = mkdisp(d6, has);
   if (n > 0) hipLaunchKernelGGL(k_back_project, g1(n), dim3(256), 0, st, n, u, v, f, pan, tilt, D, has, xy, rays);
+}
+void launch_back_project_exact(int64_t n, double u, double v, double f, double pan, double tilt, const double* d6,
+                               const double* xy, double* rays, uint8_t* valid, hipStream_t st) {
+  int has;
+  Disp D = mkdisp(d6, has);
+  if (n > 0)
+    hipLaunchKernelGGL(k_back_project_exact, g1(n), dim3(256), 0, st, n, u, v, f, pan, tilt, D, has, xy, rays, valid);
 }
 void launch_h_jacobian(int64_t n, double u, double v, double f, double pan, double tilt, const double* d6,
                        const double* rays, double* H, hipStream_t st) {

@@ -2,6 +2,7 @@
 //   rot_tp          R_tilt R_pan (ptz_camera.py:73-79)
 //   project_ray_mat PTZCamera.project_ray (ptz_camera.py:191-210): K (R p + d), signed q2
 //   back_project    PTZCamera.back_project_to_ray (ptz_camera.py:287-312)
+//   back_project_exact  the exact inverse of project_ray_mat under a displacement
 #pragma once
 #include "ptzba_common.h"
 
@@ -38,6 +39,30 @@ __device__ __forceinline__ void back_project(double u, double v, double f, doubl
 struct Disp {
   double d[6];
 };
+
+// The exact inverse of project_ray_mat: with n = ((x - u) / f, (y - v) / f, 1) and d = d(f), the model's direction
+// p = (p0, p1, 1) satisfies R p + d = t n, so t = (1 + (R^T d)_z) / (R^T n)_z and p = t R^T n - R^T d (back_project
+// subtracts d from the z = 1 point instead, which inverts the projection only for d = 0).  Returns false, with NaN
+// angles, when (R^T n)_z <= 0, t <= 0 or the result is not finite: the pixel has no ray in the (theta, phi) chart.
+__device__ __forceinline__ bool back_project_exact(double u, double v, double f, const double R[3][3], const Disp& D,
+                                                   bool has_d, double x, double y, double& th, double& ph) {
+  const double n[3] = {(x - u) / f, (y - v) / f, 1.0};
+  double d[3] = {0.0, 0.0, 0.0};
+  if (has_d)
+    for (int k = 0; k < 3; ++k) d[k] = D.d[k] + D.d[3 + k] * f;
+  double rn[3], rd[3];
+  for (int k = 0; k < 3; ++k) {
+    rn[k] = R[0][k] * n[0] + R[1][k] * n[1] + R[2][k] * n[2];
+    rd[k] = R[0][k] * d[0] + R[1][k] * d[1] + R[2][k] * d[2];
+  }
+  const double t = (1.0 + rd[2]) / rn[2];
+  const double p0 = t * rn[0] - rd[0], p1 = t * rn[1] - rd[1];
+  th = atan(p0) / PTZ_D2R;
+  ph = atan(-p1 / sqrt(p0 * p0 + 1.0)) / PTZ_D2R;
+  const bool ok = rn[2] > 0.0 && t > 0.0 && isfinite(th) && isfinite(ph);
+  if (!ok) th = ph = __builtin_nan("");
+  return ok;
+}
 
 __device__ __forceinline__ void project_ray_mat(double u, double v, double f, const double R[3][3], const Disp& D,
                                                 bool has_d, double th, double ph, double& x, double& y) {

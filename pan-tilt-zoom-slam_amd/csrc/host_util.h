@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -79,6 +80,21 @@ inline int select_device(int device) {
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail("no HIP device available");
   if (device < 0 || device >= n) return fail("device %d out of range (%d devices)", device, n);
   if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice(%d) failed", device);
+  return 0;
+}
+
+// The optional displacement argument of the relocalisation entry points (ptz_refine_poses_disp, ptz_pose_ransac_disp):
+// d6 = in when it holds a non-zero value, nullptr for NULL or six zeros (the displacement-free kernels); a non-finite
+// value is refused.
+inline int displacement_arg(const double* in, const double*& d6) {
+  d6 = nullptr;
+  if (!in) return 0;
+  bool any = false;
+  for (int k = 0; k < 6; ++k) {
+    if (!std::isfinite(in[k])) return fail("displacement: non-finite value at index %d", k);
+    any = any || in[k] != 0.0;
+  }
+  if (any) d6 = in;
   return 0;
 }
 

@@ -27,6 +27,7 @@ struct RefineArgs {
   double* cost_out;
   int* iters_out;
   int* status_out;
+  double dc[3], dk[3];  // projection-centre displacement d(f) = dc + dk f; read by the DISP instantiations alone
 };
 
 // LDS of one rf_lm call (a __shared__ object of the calling kernel)
@@ -55,8 +56,9 @@ __device__ __forceinline__ void block_sum(double (&x)[NV], double (*red)[NV]) {
   __syncthreads();
 }
 
-// cost (0.5 sum rho) and, with JAC, J^T W J (upper 6) and J^T W r (3) at pose p
-template <bool JAC>
+// cost (0.5 sum rho) and, with JAC, J^T W J (upper 6) and J^T W r (3) at pose p; with DISP under the displaced model
+// K (R p + d(f)) of ptz_project_disp, whose Jacobian carries the extended f column
+template <bool JAC, bool DISP>
 __device__ void rf_eval(const RefineArgs& a, int h, const double p[3], double (&out)[10], double (*red)[10]) {
   const FrameTab<double> F = make_frame_tab<double>(p[0], p[1], p[2]);
   double acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -65,8 +67,13 @@ __device__ void rf_eval(const RefineArgs& a, int h, const double p[3], double (&
     const int64_t c = a.sub_off ? (int64_t)a.sub_idx[k] : k;
     const RayTab<double> R = make_ray_tab<double>(a.rays[2 * c], a.rays[2 * c + 1]);
     double x, y, J[2][5];
-    if (JAC) ptz_project_jac<double>(F, R, a.u, a.v, x, y, J);
-    else ptz_project<double>(F, R, a.u, a.v, x, y);
+    if (DISP) {
+      if (JAC) ptz_project_jac_disp<double>(F, R, a.u, a.v, a.dc, a.dk, x, y, J);
+      else ptz_project_disp<double>(F, R, a.u, a.v, a.dc, a.dk, x, y);
+    } else {
+      if (JAC) ptz_project_jac<double>(F, R, a.u, a.v, x, y, J);
+      else ptz_project<double>(F, R, a.u, a.v, x, y);
+    }
     const double rx = x - a.pts[2 * c], ry = y - a.pts[2 * c + 1];
     double wx = 1, wy = 1, c2;
     if (a.loss == PTZBA_LOSS_LINEAR) {
@@ -103,11 +110,12 @@ __device__ void rf_eval(const RefineArgs& a, int h, const double p[3], double (&
 
 // The LM loop of hypothesis h from pose p (in/out), run by all RF_THREADS threads of the workgroup.  Every thread
 // returns the same p; thread 0 alone holds cost, it (accepted iterations) and status (2 ftol, 3 xtol, 0 max_iter,
-// -1 no decrease).
+// -1 no decrease).  DISP selects the camera model of rf_eval; the damping, the acceptance and the stop rules are one code.
+template <bool DISP>
 __device__ __forceinline__ void rf_lm(const RefineArgs& a, int h, double (&p)[3], double& cost, int& it, int& status,
                                       RefineShared& S) {
   double lin[10];
-  rf_eval<true>(a, h, p, lin, S.red);
+  rf_eval<true, DISP>(a, h, p, lin, S.red);
   cost = lin[9];
   double lam = 1e-4, nu = 2.0, D[3] = {0, 0, 0};
   it = 0;
@@ -145,7 +153,7 @@ __device__ __forceinline__ void rf_lm(const RefineArgs& a, int h, double (&p)[3]
     __syncthreads();
     const double t[3] = {S.trial[0], S.trial[1], S.trial[2]};
     double tr[10];
-    rf_eval<false>(a, h, t, tr, S.red);
+    rf_eval<false, DISP>(a, h, t, tr, S.red);
     if (threadIdx.x == 0) {
       const double new_cost = tr[9];
       const double actual = cost - new_cost;
@@ -174,7 +182,7 @@ __device__ __forceinline__ void rf_lm(const RefineArgs& a, int h, double (&p)[3]
     if (acc) {
       ++it;
       p[0] = t[0]; p[1] = t[1]; p[2] = t[2];
-      if (!stop) rf_eval<true>(a, h, p, lin, S.red);
+      if (!stop) rf_eval<true, DISP>(a, h, p, lin, S.red);
     }
     __syncthreads();
     if (stop) break;

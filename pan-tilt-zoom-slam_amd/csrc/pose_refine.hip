@@ -10,6 +10,8 @@
 // Hypotheses share the correspondence set or take CSR subsets of it (preemptive-RANSAC style batches,
 // SURVEY §8f-3).
 // The LM loop itself is the device function rf_lm of pose_lm.h (the pose RANSAC refits with it too).
+// `ptz_refine_poses_disp` runs the same loop under the displaced camera K (R p + d(f)): the DISP
+// instantiation of the kernel, with the six displacement values by value in RefineArgs.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -22,13 +24,14 @@
 
 namespace ptzba {
 
+template <bool DISP>
 __global__ __launch_bounds__(RF_THREADS) void k_refine_poses(RefineArgs a) {
   __shared__ RefineShared S;
   const int h = blockIdx.x;
   double p[3] = {a.ptz[3 * h], a.ptz[3 * h + 1], a.ptz[3 * h + 2]};
   double cost;
   int it, status;
-  rf_lm(a, h, p, cost, it, status, S);
+  rf_lm<DISP>(a, h, p, cost, it, status, S);
   if (threadIdx.x == 0) {
     a.ptz[3 * h] = p[0];
     a.ptz[3 * h + 1] = p[1];
@@ -43,10 +46,11 @@ __global__ __launch_bounds__(RF_THREADS) void k_refine_poses(RefineArgs a) {
 
 using namespace ptzba;
 
-int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, int64_t n_corr, const double* rays,
-                     const double* points, double u, double v, const int64_t* subset_offsets,
-                     const int32_t* subset_index, const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
-                     int32_t* status_out) {
+// d6: the six displacement values, or nullptr for the displacement-free kernel
+static int refine_poses(int device, int32_t n_hyp, double* ptz_inout, int64_t n_corr, const double* rays,
+                        const double* points, double u, double v, const int64_t* subset_offsets,
+                        const int32_t* subset_index, const ptz_refine_opts* opts, const double* d6, double* cost_out,
+                        int32_t* iters_out, int32_t* status_out) {
   if (n_hyp < 0 || n_corr < 0) return fail("bad sizes");
   if (n_hyp == 0) return 0;
   if (!ptz_inout || (n_corr > 0 && (!rays || !points))) return fail("null argument");
@@ -98,11 +102,34 @@ int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, int64_t n_cor
   a.cost_out = dcost.as<double>();
   a.iters_out = dit.as<int>();
   a.status_out = dst.as<int>();
-  hipLaunchKernelGGL(k_refine_poses, dim3(n_hyp), dim3(RF_THREADS), 0, nullptr, a);
+  for (int k = 0; k < 3; ++k) {
+    a.dc[k] = d6 ? d6[k] : 0.0;
+    a.dk[k] = d6 ? d6[3 + k] : 0.0;
+  }
+  if (d6) hipLaunchKernelGGL(k_refine_poses<true>, dim3(n_hyp), dim3(RF_THREADS), 0, nullptr, a);
+  else hipLaunchKernelGGL(k_refine_poses<false>, dim3(n_hyp), dim3(RF_THREADS), 0, nullptr, a);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(ptz_inout, dptz.p, (size_t)n_hyp * 24, hipMemcpyDeviceToHost));
   if (cost_out) HIPCHK(hipMemcpy(cost_out, dcost.p, (size_t)n_hyp * 8, hipMemcpyDeviceToHost));
   if (iters_out) HIPCHK(hipMemcpy(iters_out, dit.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost));
   if (status_out) HIPCHK(hipMemcpy(status_out, dst.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost));
   return 0;
+}
+
+int ptz_refine_poses(int device, int32_t n_hyp, double* ptz_inout, int64_t n_corr, const double* rays,
+                     const double* points, double u, double v, const int64_t* subset_offsets,
+                     const int32_t* subset_index, const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
+                     int32_t* status_out) {
+  return refine_poses(device, n_hyp, ptz_inout, n_corr, rays, points, u, v, subset_offsets, subset_index, opts, nullptr,
+                      cost_out, iters_out, status_out);
+}
+
+int ptz_refine_poses_disp(int device, int32_t n_hyp, double* ptz_inout, int64_t n_corr, const double* rays,
+                          const double* points, double u, double v, const int64_t* subset_offsets,
+                          const int32_t* subset_index, const ptz_refine_opts* opts, double* cost_out, int32_t* iters_out,
+                          int32_t* status_out, const double* displacement6) {
+  const double* d6 = nullptr;
+  if (displacement_arg(displacement6, d6)) return -1;
+  return refine_poses(device, n_hyp, ptz_inout, n_corr, rays, points, u, v, subset_offsets, subset_index, opts, d6,
+                      cost_out, iters_out, status_out);
 }

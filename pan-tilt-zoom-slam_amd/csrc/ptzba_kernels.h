@@ -585,6 +585,9 @@ void launch_project_rays(int64_t n, double u, double v, double f, double pan, do
                          const double* rays, double* xy, hipStream_t st);
 void launch_back_project(int64_t n, double u, double v, double f, double pan, double tilt, const double* disp6,
                          const double* xy, double* rays, hipStream_t st);
+// the exact inverse of launch_project_rays; valid [n] (0: no ray in the chart, the ray is NaN) may be nullptr
+void launch_back_project_exact(int64_t n, double u, double v, double f, double pan, double tilt, const double* disp6,
+                               const double* xy, double* rays, uint8_t* valid, hipStream_t st);
 void launch_h_jacobian(int64_t n, double u, double v, double f, double pan, double tilt, const double* disp6,
                        const double* rays, double* H, hipStream_t st);
 

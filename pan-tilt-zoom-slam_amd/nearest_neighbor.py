@@ -12,6 +12,11 @@ is the reference's: squared L2 distance < 2000 (FLANN's nn_index returns squared
 (nearest_neighbor.py:86-122, without its .mat dump) -- it needs a close starting pose and has no defence against
 wrong matches.  `relocalize_robust` needs neither: the matches go to the two-point PTZ pose RANSAC
 (ptzba.pose_ransac), which samples pose candidates in closed form, scores them all and refits the best on its inliers.
+
+`displacement=`: the camera's six projection-centre displacement values (the model the tracker and, with
+ba_displacement, the bundle adjuster project with).  The map then stores the exact inverse projections of its
+keyframes' features (ptzba.back_project_rays(exact=True); the reference's back_project_to_ray is only an approximate
+inverse once the displacement is not zero), and both relocalisations fit the pose under the displaced model.
 """
 import itertools
 
@@ -25,8 +30,14 @@ class NNBasedMap(Map):
     MAX_SQ_DIST = 2000.0  # nearest_neighbor.py:40
     _ids = itertools.count(1)  # device descriptor-set keys: a range of their own, two per instance
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, displacement=None):
         super().__init__('sift')
+        self.displacement = None  # six values, or None (also for six zeros, as PtzSlam._disp reads a camera's)
+        if displacement is not None:
+            d = np.asarray(displacement, np.float64).reshape(-1)
+            if d.shape != (6,) or not np.isfinite(d).all():
+                raise ValueError("displacement: six finite values expected")
+            self.displacement = d.copy() if np.any(d != 0) else None
         self.global_des = np.ndarray([0, 128], dtype=np.float32)  # [N, 128], row k belongs to global_ray[k]
         self.device = device
         k = next(NNBasedMap._ids)
@@ -66,12 +77,20 @@ class NNBasedMap(Map):
         return keep.tolist(), idx[keep, 0].tolist()
 
     def add_keyframe_without_ba(self, keyframe, verbose=False):
-        """nearest_neighbor.py:46-56: append the keyframe, its features' rays at its pose, and their descriptors."""
+        """nearest_neighbor.py:46-56: append the keyframe, its features' rays at its pose, and their descriptors.
+        With a displacement the rays are the exact inverse projections, and a feature without a ray in the
+        (theta, phi) chart is left out of global_ray and global_des together."""
         super().add_keyframe_without_ba(keyframe, verbose)
         pts = _points_array(keyframe.feature_pts)
-        rays = ptzba.back_project_rays(keyframe.u, keyframe.v, keyframe.f, keyframe.pan, keyframe.tilt, pts)
+        des = np.asarray(keyframe.feature_des, np.float32).reshape(len(pts), -1)
+        if self.displacement is None:
+            rays = ptzba.back_project_rays(keyframe.u, keyframe.v, keyframe.f, keyframe.pan, keyframe.tilt, pts)
+        else:
+            rays, valid = ptzba.back_project_rays(keyframe.u, keyframe.v, keyframe.f, keyframe.pan, keyframe.tilt, pts,
+                                                  self.displacement, exact=True)
+            rays, des = rays[valid], des[valid]
         self.global_ray = np.vstack([self.global_ray, rays])
-        self.global_des = np.vstack([self.global_des, np.asarray(keyframe.feature_des, np.float32).reshape(len(pts), -1)])
+        self.global_des = np.vstack([self.global_des, des])
 
     def add_keyframes(self, keyframe_list):
         for keyframe in keyframe_list:
@@ -79,11 +98,15 @@ class NNBasedMap(Map):
         self.build_kdtree()
 
     @staticmethod
-    def compute_residual(pose, rays, points, u, v):
-        """nearest_neighbor.py:64-83: interleaved reprojection errors of `rays` at `pose` against `points`."""
+    def compute_residual(pose, rays, points, u, v, displacement=None):
+        """nearest_neighbor.py:64-83: interleaved reprojection errors of `rays` at `pose` against `points`; with
+        displacement= (a map's `displacement`) under the displaced camera."""
         rays = np.asarray(rays, np.float64).reshape(-1, 2)
         points = np.asarray(points, np.float64).reshape(-1, 2)
         n = len(rays)
+        if displacement is not None:
+            xy = ptzba.project_rays(u, v, pose[2], pose[0], pose[1], rays, displacement)
+            return (xy - points).reshape(-1)
         x, y = ptzba.ray_to_image(u, v, np.full(n, pose[2]), np.full(n, pose[0]), np.full(n, pose[1]), rays[:, 0],
                                   rays[:, 1])
         return np.stack([x - points[:, 0], y - points[:, 1]], 1).reshape(-1)
@@ -100,17 +123,18 @@ class NNBasedMap(Map):
         pose = np.array([keyframe.pan, keyframe.tilt, keyframe.f], np.float64)
         if len(rays) == 0:
             return pose
-        ptz, cost, its, status = ptzba.refine_poses(keyframe.u, keyframe.v, pose[None], rays, points, ftol=1e-4)
+        ptz, cost, its, status = ptzba.refine_poses(keyframe.u, keyframe.v, pose[None], rays, points, ftol=1e-4,
+                                                    displacement=self.displacement)
         return ptz[0]
 
-    def relocalize_robust(self, keyframe, threshold=3.0, n_hyp=1024, seed=0):
+    def relocalize_robust(self, keyframe, threshold=3.0, n_hyp=1024, seed=0, ftol=1e-4, xtol=1e-8):
         """Pose of `keyframe` from its features alone (its pan / tilt / f are not read): find_nearest, then the
-        two-point pose RANSAC.  Returns (ptz [3] or None, inlier count, found)."""
+        two-point pose RANSAC (ftol, xtol: its refit's).  Returns (ptz [3] or None, inlier count, found)."""
         rays, points = self._matches(keyframe)
         if len(rays) < 2:
             return None, 0, False
         r = ptzba.pose_ransac(keyframe.u, keyframe.v, rays, points, threshold=threshold, n_hyp=n_hyp, seed=seed,
-                              device=self.device)
+                              ftol=ftol, xtol=xtol, device=self.device, displacement=self.displacement)
         return r.ptz, r.n_inliers, r.found
 
 

@@ -240,7 +240,8 @@ class PtzSlam:
             if len(self.keyframe_map.keyframe_list) > 1:
                 from relocalization import relocalization_camera
                 lost_pose = camera.pan, camera.tilt, camera.focal_length
-                relocalize_pose = relocalization_camera(self.keyframe_map, img, lost_pose)
+                relocalize_pose = relocalization_camera(self.keyframe_map, img, lost_pose,
+                                                        displacement=self.keyframe_map.displacement_for_reloc())
                 camera.set_ptz(relocalize_pose)
             else:
                 print("Warning: Not enough keyframes for relocalization.")

@@ -227,6 +227,7 @@ def lib():
         "ptz_image_to_ray": ([I, I64, D, D, V, V, V, V, V, V, V], I),
         "ptz_project_rays": ([I, I64, D, D, D, D, D, V, V, V], I),
         "ptz_back_project_rays": ([I, I64, D, D, D, D, D, V, V, V], I),
+        "ptz_back_project_rays_exact": ([I, I64, D, D, D, D, D, V, V, V, V], I),
         "ptz_h_jacobian": ([I, I64, D, D, D, D, D, V, V, V], I),
         "ptzba_build_landmarks": ([I32, V, I64, V, V, V, V, V, V, V, V], I),
         "ptzba_coupling_window": ([I32, I32, I64, V, V, V], I),
@@ -252,6 +253,9 @@ def lib():
         "ptz_refine_poses": ([I, I32, V, I64, V, V, D, D, V, V, POINTER(ptz_refine_opts), V, V, V], I),
         "ptz_pose_ransac": ([I, I64, V, V, D, D, POINTER(ptz_pose_ransac_opts), V, V, POINTER(c_int32), POINTER(c_int32),
                             V, POINTER(c_int32), POINTER(c_double), POINTER(c_int32)], I),
+        "ptz_refine_poses_disp": ([I, I32, V, I64, V, V, D, D, V, V, POINTER(ptz_refine_opts), V, V, V, V], I),
+        "ptz_pose_ransac_disp": ([I, I64, V, V, D, D, POINTER(ptz_pose_ransac_opts), V, V, POINTER(c_int32),
+                                 POINTER(c_int32), V, POINTER(c_int32), POINTER(c_double), POINTER(c_int32), V], I),
         "ptz_corner_min_eig": ([I, I32, I32, V, V, V], I),
         "ptzba_partition_landmarks": ([I32, I32, I64, V, V, I32, I32, V, POINTER(c_int32), V], I),
         "ptzba_set_exchange_hook": ([V, EXCHANGE_FN, V], I),
@@ -310,6 +314,7 @@ EXPORTED_SYMBOLS = [
     "ptzba_set_pose_priors", "ptzba_pose_prior_info", "ptzba_marginal_prior", "ptzba_set_marginal_prior",
     "ptzba_marginal_prior_info", "ptzba_set_ray_priors", "ptzba_ray_prior_info", "ptzba_covariance_joint",
     "ptzba_set_displacement", "ptzba_displacement_info",
+    "ptz_back_project_rays_exact", "ptz_refine_poses_disp", "ptz_pose_ransac_disp",
     "ptzba_solver_buffers",
 ]
 
@@ -374,11 +379,19 @@ def project_rays(u, v, f, pan, tilt, rays, displacement=None, device=0):
     return out
 
 
-def back_project_rays(u, v, f, pan, tilt, points, displacement=None, device=0):
-    """Batched PTZCamera.back_project_to_ray (ptz_camera.py:287-312): [n,2] points -> [n,2] rays."""
+def back_project_rays(u, v, f, pan, tilt, points, displacement=None, device=0, exact=False):
+    """Batched PTZCamera.back_project_to_ray (ptz_camera.py:287-312): [n,2] points -> [n,2] rays.  With a
+    displacement that is only an approximate inverse of project_rays (the reference subtracts d(f) from the z = 1
+    point).  exact=True is the exact inverse (ptz_back_project_rays_exact) and returns (rays [n,2], valid [n] bool): a
+    pixel without a ray in the (theta, phi) chart is not valid and its ray is NaN."""
     pts = _f64(points, (-1, 2))
     out = np.empty_like(pts)
     d = None if displacement is None else _f64(displacement, (6,))
+    if exact:
+        valid = np.zeros(len(pts), np.uint8)
+        _check(lib().ptz_back_project_rays_exact(device, len(pts), u, v, float(f), float(pan), float(tilt), _ptr(d),
+                                                 _ptr(pts), _ptr(out), _ptr(valid)), "ptz_back_project_rays_exact")
+        return out, valid.astype(bool)
     _check(lib().ptz_back_project_rays(device, len(pts), u, v, float(f), float(pan), float(tilt), _ptr(d), _ptr(pts),
                                        _ptr(out)), "ptz_back_project_rays")
     return out
@@ -618,10 +631,12 @@ def orb(img, nfeatures=500, descriptor="orb", device=None):
 
 
 def refine_poses(u, v, init_ptz, rays, points, subsets=None, ftol=1e-4, xtol=1e-8, max_iter=100, loss=LOSS_LINEAR,
-                 f_scale=1.0, device=0):
+                 f_scale=1.0, device=0, displacement=None):
     """Pose-only LM with the rays fixed (relocalization.py:22-40, 186), batched over hypotheses.
     init_ptz [n_hyp, 3]; rays / points [n, 2]; subsets: optional list of index arrays (one per
     hypothesis).  loss: a LOSS_* id or scipy's name (IRLS weights for the robust ones).
+    displacement: the camera's six projection-centre displacement values (ptz_refine_poses_disp: the residual of
+    project_rays' model); None or zeros: the displacement-free model.
     Returns (ptz [n_hyp, 3], cost [n_hyp], iterations [n_hyp], status [n_hyp])."""
     ptz = _f64(init_ptz).reshape(-1, 3).copy()
     rays = _f64(rays).reshape(-1, 2)
@@ -641,9 +656,15 @@ def refine_poses(u, v, init_ptz, rays, points, subsets=None, ftol=1e-4, xtol=1e-
     its = np.zeros(n_hyp, np.int32)
     st = np.zeros(n_hyp, np.int32)
     opts = ptz_refine_opts(int(max_iter), loss_id(loss), float(ftol), float(xtol), float(f_scale))
-    _check(lib().ptz_refine_poses(int(device), n_hyp, _ptr(ptz), len(rays), _ptr(rays), _ptr(points), float(u),
-                                  float(v), _ptr(off), _ptr(idx), ctypes.byref(opts), _ptr(cost), _ptr(its), _ptr(st)),
-           "ptz_refine_poses")
+    if displacement is None:
+        _check(lib().ptz_refine_poses(int(device), n_hyp, _ptr(ptz), len(rays), _ptr(rays), _ptr(points), float(u),
+                                      float(v), _ptr(off), _ptr(idx), ctypes.byref(opts), _ptr(cost), _ptr(its),
+                                      _ptr(st)), "ptz_refine_poses")
+    else:
+        d6 = _f64(displacement, (6,))
+        _check(lib().ptz_refine_poses_disp(int(device), n_hyp, _ptr(ptz), len(rays), _ptr(rays), _ptr(points), float(u),
+                                           float(v), _ptr(off), _ptr(idx), ctypes.byref(opts), _ptr(cost), _ptr(its),
+                                           _ptr(st), _ptr(d6)), "ptz_refine_poses_disp")
     return ptz, cost, its, st
 
 
@@ -661,12 +682,14 @@ class PoseRansacResult:
 
 
 def pose_ransac(u, v, rays, points, threshold=3.0, n_hyp=1024, seed=0, min_inliers=3, ftol=1e-4, xtol=1e-8,
-                max_iter=100, device=None):
+                max_iter=100, device=None, displacement=None):
     """Robust (pan, tilt, f) from ray-pixel correspondences without an initial pose (ptz_pose_ransac): n_hyp two-point
     samples, each giving up to four closed-form pose candidates, all scored against every correspondence (inlier:
     in front of the camera, reprojection error < threshold px); the candidate with the most inliers (ties: lowest
     sample, then candidate order) is refitted by the pose-only LM on its inliers.  rays / points [n, 2], n >= 2.
-    min_inliers below 3 is taken as 3.  Returns a PoseRansacResult."""
+    min_inliers below 3 is taken as 3.  displacement: the camera's six projection-centre displacement values
+    (ptz_pose_ransac_disp: the closed form then starts a fixed number of Newton steps in f, and scoring and refit use
+    project_rays' model); None or zeros: the displacement-free model.  Returns a PoseRansacResult."""
     rays = _f64(rays).reshape(-1, 2)
     points = _f64(points).reshape(-1, 2)
     if len(rays) != len(points):
@@ -679,10 +702,17 @@ def pose_ransac(u, v, rays, points, threshold=3.0, n_hyp=1024, seed=0, min_inlie
     mask = np.zeros(max(n, 1), np.uint8)
     best, hin, nin, st = c_int32(-1), c_int32(0), c_int32(0), c_int32(1)
     cost = c_double(np.nan)
-    _check(lib().ptz_pose_ransac(default_device() if device is None else int(device), n, _ptr(rays), _ptr(points),
-                                 float(u), float(v), ctypes.byref(opts), _ptr(ptz), _ptr(hyp), ctypes.byref(best),
-                                 ctypes.byref(hin), _ptr(mask), ctypes.byref(nin), ctypes.byref(cost),
-                                 ctypes.byref(st)), "ptz_pose_ransac")
+    dev = default_device() if device is None else int(device)
+    if displacement is None:
+        _check(lib().ptz_pose_ransac(dev, n, _ptr(rays), _ptr(points), float(u), float(v), ctypes.byref(opts),
+                                     _ptr(ptz), _ptr(hyp), ctypes.byref(best), ctypes.byref(hin), _ptr(mask),
+                                     ctypes.byref(nin), ctypes.byref(cost), ctypes.byref(st)), "ptz_pose_ransac")
+    else:
+        d6 = _f64(displacement, (6,))
+        _check(lib().ptz_pose_ransac_disp(dev, n, _ptr(rays), _ptr(points), float(u), float(v), ctypes.byref(opts),
+                                          _ptr(ptz), _ptr(hyp), ctypes.byref(best), ctypes.byref(hin), _ptr(mask),
+                                          ctypes.byref(nin), ctypes.byref(cost), ctypes.byref(st), _ptr(d6)),
+               "ptz_pose_ransac_disp")
     found = st.value == 0
     return PoseRansacResult(ptz=ptz if found else None, ptz_hyp=hyp if best.value >= 0 else None,
                             best_sample=int(best.value), hyp_inliers=int(hin.value), mask=mask[:n].astype(bool),

@@ -70,10 +70,12 @@ class Map:
     (the one the tracker projects with), bundle_adjustment's displacement=.  Six values, or True: the `displacement`
     attribute of the first keyframe that carries a non-zero one (read as PtzSlam._disp reads a camera's: all zero or
     missing is none).  The map keeps the value once it has it -- the keyframes a bundle adjustment hands back are new
-    objects -- and copies it onto those keyframes."""
+    objects -- and copies it onto those keyframes.  reloc_displacement: relocalisation against this map
+    (PtzSlam.relocalize -> relocalization_camera) runs under the displacement too.  Six values, or True: the value
+    ba_displacement resolved to, or else the first keyframe's non-zero `displacement` attribute."""
 
     def __init__(self, feature_method, cache_correspondences=True, max_ba_frame=None, marginalize=False,
-                 ba_displacement=False):
+                 ba_displacement=False, reloc_displacement=False):
         assert feature_method in ("sift", "orb", "latch")
         self.global_ray = np.ndarray([0, 2])
         self.keyframe_list = []
@@ -89,6 +91,12 @@ class Map:
             self.ba_displacement = self._nonzero6(ba_displacement)
             if self.ba_displacement is None:
                 raise ValueError("ba_displacement: six finite values, not all zero, expected (or True / False)")
+        self.reloc_displacement = None  # the six values, once known
+        self._reloc_displacement_from_map = reloc_displacement is True
+        if reloc_displacement is not True and reloc_displacement is not False and reloc_displacement is not None:
+            self.reloc_displacement = self._nonzero6(reloc_displacement)
+            if self.reloc_displacement is None:
+                raise ValueError("reloc_displacement: six finite values, not all zero, expected (or True / False)")
 
     @staticmethod
     def _nonzero6(d):
@@ -107,6 +115,17 @@ class Map:
                 if self.ba_displacement is not None:
                     break
         return self.ba_displacement
+
+    def displacement_for_reloc(self):
+        """The displacement relocalisation runs under (None: none); with reloc_displacement=True the value the bundle
+        adjustments use, or else that of the first keyframe that carries a non-zero one."""
+        if self.reloc_displacement is None and self._reloc_displacement_from_map:
+            self.reloc_displacement = self.ba_displacement
+            for k in self.keyframe_list:
+                if self.reloc_displacement is not None:
+                    break
+                self.reloc_displacement = self._nonzero6(getattr(k, "displacement", None))
+        return self.reloc_displacement
 
     def add_first_keyframe(self, keyframe, verbose=False):
         assert isinstance(keyframe, KeyFrame)
@@ -207,17 +226,34 @@ class RandomForestMap:
     random-forest map files (rf_map, C++) are not part of this build: `relocalize` searches a nearest-neighbour
     descriptor -> ray database over the keyframes (nearest_neighbor.NNBasedMap, exact kNN on the GPU) where the
     reference walks its forest, and estimates the pose from the matches by the two-point PTZ pose RANSAC where the
-    reference runs its preemptive RANSAC (rf_map/util/ptz_pose_estimation.cpp)."""
+    reference runs its preemptive RANSAC (rf_map/util/ptz_pose_estimation.cpp).  reloc_displacement: `relocalize`
+    builds its database and fits the pose under the camera's projection-centre displacement; six values, or True: the
+    first keyframe's non-zero `displacement` attribute."""
 
-    def __init__(self, max_ba_frame=10, feature_method="sift", cache_correspondences=True):
+    def __init__(self, max_ba_frame=10, feature_method="sift", cache_correspondences=True, reloc_displacement=False):
         self.keyframe_list = []
         self.feature_method = feature_method
         self.max_ba_frame = max_ba_frame
         self.global_ray = np.ndarray([0, 2])
         self.ba_options = {}
         self.correspondences = CorrespondenceCache() if cache_correspondences else None
-        self.reloc_options = {}  # threshold / n_hyp / seed of relocalize's pose RANSAC
+        self.reloc_options = {}  # threshold / n_hyp / seed / ftol / xtol of relocalize's pose RANSAC
         self._nn_map = None  # the descriptor -> ray database of relocalize, rebuilt after add_keyframe
+        self.reloc_displacement = None  # the six values, once known
+        self._reloc_displacement_from_keyframes = reloc_displacement is True
+        if reloc_displacement is not True and reloc_displacement is not False and reloc_displacement is not None:
+            self.reloc_displacement = Map._nonzero6(reloc_displacement)
+            if self.reloc_displacement is None:
+                raise ValueError("reloc_displacement: six finite values, not all zero, expected (or True / False)")
+
+    def displacement_for_reloc(self):
+        """The displacement `relocalize` runs under (None: none)."""
+        if self.reloc_displacement is None and self._reloc_displacement_from_keyframes:
+            for k in self.keyframe_list:
+                self.reloc_displacement = Map._nonzero6(getattr(k, "displacement", None))
+                if self.reloc_displacement is not None:
+                    break
+        return self.reloc_displacement
 
     def add_keyframe(self, keyframe):
         self.keyframe_list.append(keyframe)
@@ -258,7 +294,7 @@ class RandomForestMap:
         keyframes of the map at their current, bundle-adjusted poses, or `ptz` when no pose is found."""
         if self._nn_map is None:
             from nearest_neighbor import NNBasedMap
-            self._nn_map = NNBasedMap()
+            self._nn_map = NNBasedMap(displacement=self.displacement_for_reloc())
             self._nn_map.add_keyframes([k for k in self.keyframe_list if k.get_feature_num() > 0])
         pose, n_inliers, found = self._nn_map.relocalize_robust(keyframe, **self.reloc_options)
         return pose if found else np.asarray(ptz, np.float64)
